@@ -28,9 +28,17 @@ launcher, --gpus must equal WORLD_SIZE (else exit 2). ``--dry-run`` runs the
 same orchestration on CPU/gloo with no-op per-rank compute (a plumbing check:
 its timings mean nothing).
 
-Extra legs on rank 0 at N = 1:
+A plain run builds the graph, warms up, times ``--steps`` steps and prints the
+result line. ``--dump-outputs DIR`` also writes what the last timed step handed
+its caller (the poses ``Twc`` updated in place and the returned last update
+``dx``) as ``DIR/Twc.npy`` and ``DIR/dx.npy`` (float32); the inputs are seeded,
+so two builds can be compared output for output.
+
+``--full`` adds the legs below (each takes runs of its own):
   cold         — the same steps with the host plan cache off (knob plan_cache=0):
                  the per-call symbolic analysis inside the timed region
+  natural_termination — the same calls with the reference's delta_thresh = 1e-8
+and, on rank 0 at N = 1:
   roofline     — the linearize kernel timed with HIP events on its stream
                  (+ the first-iteration gathering kernel and the solve launches)
   hbm_copy     — a measured streaming-copy rate (16-B nt copy kernel) next to the 8 TB/s spec
@@ -79,6 +87,11 @@ def parse(argv=None):
     ap.add_argument("--lin-reps", type=int, default=30)
     ap.add_argument("--cold-steps", type=int, default=5)
     ap.add_argument("--natural-steps", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the cold, natural-termination, roofline, copy-rate, tracker, matching "
+                         "and CPU-baseline legs (off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (Twc, dx) as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-tracker", action="store_true")
     ap.add_argument("--dry-run", action="store_true",
@@ -135,8 +148,19 @@ def base_edges(args):
     return synthetic.make_graph(args.kf_per_gpu, 4, 4, seed=SEED, edge_range=(0, 0)).n_edges
 
 
+def dump_outputs(path, tensors):
+    """--dump-outputs: each named tensor as path/<name>.npy (float32 stays
+    float32, anything else becomes float64). A C3 run writes about 1 kB."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
 def run(args):
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dry = args.dry_run
@@ -211,17 +235,17 @@ def run(args):
         Twc.copy_(T_init)
         if world == 1 and not dry:  # the drop-in entry point itself
             if calib_mode:
-                be.gauss_newton_calib(Twc, Xs, Cs, g.K, ii, jj, idx, valid, Q, H, W, -10, 1e-6, 1.0,
-                                      10.0, 0.0, 1.5, iters, delta, info=info)
-            else:
-                be.gauss_newton_rays(Twc, Xs, Cs, ii, jj, idx, valid, Q, 0.003, 10.0, 0.0, 1.5,
-                                     iters, delta, info=info)
-        else:
-            solver.solve(iters, delta)
+                return be.gauss_newton_calib(Twc, Xs, Cs, g.K, ii, jj, idx, valid, Q, H, W, -10, 1e-6, 1.0,
+                                             10.0, 0.0, 1.5, iters, delta, info=info)
+            return be.gauss_newton_rays(Twc, Xs, Cs, ii, jj, idx, valid, Q, 0.003, 10.0, 0.0, 1.5,
+                                        iters, delta, info=info)
+        return solver.solve(iters, delta)
 
     def sync():
         if not dry:
             torch.cuda.synchronize()
+
+    returned = [None]  # what the last step handed back: [dx]
 
     def timed(nsteps, delta=0.0):
         if world > 1:
@@ -229,7 +253,7 @@ def run(args):
         sync()
         t0 = time.perf_counter()
         for _ in range(nsteps):
-            step(delta)
+            returned[0] = step(delta)
         sync()
         if world > 1:
             dist.barrier()
@@ -250,10 +274,13 @@ def run(args):
     if world == 1 and not dry:
         assert int(info[be.INFO_ITERS]) == args.iters and int(info[be.INFO_BAD_EDGE]) == 0
         assert int(info[be.INFO_SOLVE_FAIL]) == 0
+    if args.dump_outputs and rank == 0:  # before any further leg overwrites Twc / dx
+        dump_outputs(args.dump_outputs, {"Twc": Twc, "dx": returned[0][0]})
+    full = args.full
 
     # cold calls: the host symbolic analysis (ordering, fill, schedule) inside
     # the timed region, as a SLAM backend call whose edge set changed pays it
-    if dry:
+    if dry or not full:
         cold_el = None
     else:
         with be.knob("plan_cache", 0):
@@ -264,7 +291,7 @@ def run(args):
     # max_iter = 10; the device stop flag ends the loop when a step's norm
     # falls below delta, and the iterations actually run are counted
     natural = None
-    if not dry and args.natural_steps > 0:
+    if full and not dry and args.natural_steps > 0:
         step(1e-8)  # warm-up of the delta path
         nat_el = timed(args.natural_steps, 1e-8)
         nat_iters = int(solver.ops.info[0]) if world > 1 else int(info[be.INFO_ITERS])
@@ -313,6 +340,8 @@ def run(args):
                     "analysis, as a call on a changed edge set does",
         },
     }
+    if not full:  # legs of --full
+        del out["natural_termination"], out["cold"]
     if dry:
         out["dry_run"] = True
         out["data"] = "dry run: CPU/gloo orchestration with no-op compute; timings are meaningless"
@@ -320,11 +349,11 @@ def run(args):
         out["share_gpu"] = True
         out["data"] = ("rehearsal: %d ranks sharing ONE GPU over gloo (the product path, HIP compute); "
                        "not a scaling measurement" % world)
-    else:
+    elif full:
         out["roofline"] = roofline_leg(args, solver, be, Twc, T_init, ii, jj, ids, HW, gn_iters_per_s,
                                        world, dev, step if world == 1 else None, elapsed / args.steps)
 
-    if rank == 0 and world == 1 and not dry:
+    if full and rank == 0 and world == 1 and not dry:
         out["hbm_copy"] = copy_leg(be, dev)
         out["roofline"]["frac_of_measured_copy"] = round(out["roofline"]["achieved"] / out["hbm_copy"]["GB_per_s"], 4)
         if not args.no_tracker:

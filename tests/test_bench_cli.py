@@ -31,6 +31,32 @@ def test_gpus_2_spawns_two_ranks():
     assert "world_size=2" in r.stderr
 
 
+def _line(r):
+    assert r.returncode == 0, r.stderr[-2000:]
+    (line,) = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    return json.loads(line)
+
+
+def test_plain_run_dumps_outputs_and_full_adds_the_legs(tmp_path):
+    """A plain run carries the headline keys only and --dump-outputs writes the
+    last timed step's Twc and dx as float32 .npy; the extra legs' keys appear
+    only with --full."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    d = _line(_run(["--gpus", "1", "--dry-run", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert not {"cold", "natural_termination", "roofline", "hbm_copy", "tracker_c2", "cpu_baseline"} & set(d)
+    assert sorted(os.listdir(out)) == ["Twc.npy", "dx.npy"]
+    Twc, dx = np.load(out / "Twc.npy"), np.load(out / "dx.npy")
+    assert Twc.dtype == np.float32 and Twc.shape == (32, 8)
+    assert dx.dtype == np.float32 and dx.shape == (31, 7)
+    f = _line(_run(["--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "1", "--full"]))
+    assert "cold" in f and "natural_termination" in f
+
+
 def test_world_size_mismatch_is_refused():
     r = _run(["--gpus", "2", "--dry-run"], {"WORLD_SIZE": "4"})
     assert r.returncode == 2

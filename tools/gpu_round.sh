@@ -19,6 +19,6 @@ timeout -k 10 600 python -u tools/weak_emul.py > $OUT/${TAG}_weak_emul.txt 2>&1 
 cat $OUT/${TAG}_weak_emul.txt | grep -v amdgpu.ids
 fi
 if [ -z "${SKIP_BENCH:-}" ]; then
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { echo "bench failed"; tail -20 $OUT/${TAG}_bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { echo "bench failed"; tail -20 $OUT/${TAG}_bench.err; exit 1; }
 cat $OUT/${TAG}_bench.json
 fi

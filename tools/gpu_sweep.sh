@@ -10,7 +10,7 @@ TAG=${TAG:-sweep}
 mkdir -p $OUT
 cd $R
 for n in ${NS:-64 128 256}; do
-  timeout -k 10 240 python bench.py --kf-per-gpu $n --steps 3 --warmup 1 --cold-steps 2 --no-cpu --no-tracker --mode ${MODE:-calib} ${BENCH_ARGS:-} > $OUT/${TAG}_n$n.json 2> $OUT/${TAG}_n$n.err || { echo "bench n=$n failed"; tail -5 $OUT/${TAG}_n$n.err; exit 1; }
+  timeout -k 10 240 python bench.py --full --kf-per-gpu $n --steps 3 --warmup 1 --cold-steps 2 --no-cpu --no-tracker --mode ${MODE:-calib} ${BENCH_ARGS:-} > $OUT/${TAG}_n$n.json 2> $OUT/${TAG}_n$n.err || { echo "bench n=$n failed"; tail -5 $OUT/${TAG}_n$n.err; exit 1; }
   python - "$OUT/${TAG}_n$n.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

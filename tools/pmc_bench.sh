@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/${TAG:-pmc}
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-ARGS="--steps 2 --warmup 1 --no-cpu --no-tracker --lin-reps 10 --cold-steps 0 ${BENCH_ARGS:-}"
+ARGS="--full --steps 2 --warmup 1 --no-cpu --no-tracker --lin-reps 10 --cold-steps 0 ${BENCH_ARGS:-}"
 i=0
 for grp in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum" \
            "TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE" \
