@@ -1,5 +1,6 @@
 // m3s_match.hip — MI355X (gfx950) matching kernels of MASt3R-SLAM:
-// iter_proj and refine_matches (include/m3s_match.h).
+// iter_proj and refine_matches, and match_dense, which runs both with the
+// torch glue around them folded into their kernels (include/m3s_match.h).
 //
 // Both are per-pixel independent searches: one lane per (batch, pixel), 256
 // lanes per block, grid over B*N. Their reads are gathers around the pixel's
@@ -17,6 +18,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "m3s_fuse.h"
 #include "m3s_gn.h"
 #include "m3s_match.h"
 
@@ -73,23 +75,19 @@ __device__ __forceinline__ float normalized_cost(float *r, const float *p) {
   return err[0] * err[0] + err[1] * err[1] + err[2] * err[2];
 }
 
-__global__ void __launch_bounds__(kMatchThreads) iter_proj_kernel(m3s_iter_proj_args A) {
-  const int64_t gid = (int64_t)blockIdx.x * kMatchThreads + threadIdx.x;
-  if (gid >= A.B * A.N) return;
-  const int64_t b = gid / A.N;
-  const float *img = A.rays_img + b * A.H * A.W * 9;
-  const float W2 = (float)(A.W - 2), H2 = (float)(A.H - 2);
-  float u = clampf(A.p_init[2 * gid], 1.0f, W2);
-  float v = clampf(A.p_init[2 * gid + 1], 1.0f, H2);
-  const float p[3] = {A.pts_3d_norm[3 * gid], A.pts_3d_norm[3 * gid + 1], A.pts_3d_norm[3 * gid + 2]};
-  float lambda = A.lambda_init;
+// The LM loop of matching_kernels.cu:150-290 from the (clamped) start pixel
+// (u, v); returns the converged flag. One definition for iter_proj_kernel and
+// match_proj_kernel, so both run the same IEEE sequence.
+__device__ __forceinline__ bool lm_project(const float *img, int64_t W, float W2, float H2, const float (&p)[3],
+                                           int max_iter, float lambda_init, float cost_thresh, float &u, float &v) {
+  float lambda = lambda_init;
   bool conv = false;
-  for (int it = 0; it < A.max_iter; it++) {
+  for (int it = 0; it < max_iter; it++) {
     const Bilin B = bilin(u, v);
     float r[3], gx[3], gy[3];
-    sample<3>(img, A.W, B, 0, r);
-    sample<3>(img, A.W, B, 3, gx);
-    sample<3>(img, A.W, B, 6, gy);
+    sample<3>(img, W, B, 0, r);
+    sample<3>(img, W, B, 3, gx);
+    sample<3>(img, W, B, 6, gy);
     // error of the normalised ray (matching_kernels.cu:184-198)
     const float r_norm = sqrtf(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
     const float r_norm_inv = (float)(1.0 / (double)r_norm);
@@ -116,21 +114,81 @@ __global__ void __launch_bounds__(kMatchThreads) iter_proj_kernel(m3s_iter_proj_
     // cost at the candidate (matching_kernels.cu:229-262)
     const Bilin Bn = bilin(u_new, v_new);
     float rn[3];
-    sample<3>(img, A.W, Bn, 0, rn);
+    sample<3>(img, W, Bn, 0, rn);
     const float new_cost = normalized_cost(rn, p);
     if (new_cost < cost) {
       u = u_new;
       v = v_new;
       lambda = (float)((double)lambda * 0.1);
-      conv = new_cost < A.cost_thresh;
+      conv = new_cost < cost_thresh;
     } else {
       lambda = (float)((double)lambda * 10.0);
-      conv = cost < A.cost_thresh;
+      conv = cost < cost_thresh;
     }
   }
+  return conv;
+}
+
+__global__ void __launch_bounds__(kMatchThreads) iter_proj_kernel(m3s_iter_proj_args A) {
+  const int64_t gid = (int64_t)blockIdx.x * kMatchThreads + threadIdx.x;
+  if (gid >= A.B * A.N) return;
+  const int64_t b = gid / A.N;
+  const float *img = A.rays_img + b * A.H * A.W * 9;
+  const float W2 = (float)(A.W - 2), H2 = (float)(A.H - 2);
+  float u = clampf(A.p_init[2 * gid], 1.0f, W2);
+  float v = clampf(A.p_init[2 * gid + 1], 1.0f, H2);
+  const float p[3] = {A.pts_3d_norm[3 * gid], A.pts_3d_norm[3 * gid + 1], A.pts_3d_norm[3 * gid + 2]};
+  const bool conv = lm_project(img, A.W, W2, H2, p, A.max_iter, A.lambda_init, A.cost_thresh, u, v);
   A.p_new[2 * gid] = u;
   A.p_new[2 * gid + 1] = v;
   A.converged[gid] = conv ? 1 : 0;
+}
+
+// ---- match_dense, first half: projection with a built-in start pixel and the
+// occlusion test of matching.py:69-76 as its epilogue. Lane n of batch b
+// starts at its own pixel (n % W, n / W), or at idx_init's pixel
+// (lin_to_pixel(idx).float(), matching.py:32-41; torch's floor % and //),
+// runs lm_project, truncates the result (already clamped to [1, W-2] x
+// [1, H-2], so (int) equals the reference's .long()) and tests
+// |X11[b, pv, pu] - X21[b, n]| < dist_thresh in fp32 without contraction.
+// Block 0 also zeroes n_valid for the refine epilogue that follows on the
+// same stream.
+struct MatchProjArgs {
+  const float *rays_img, *pts_norm, *X11, *X21;
+  const int64_t *idx_init;  // [B, N] or null
+  int64_t B, H, W, N;
+  int max_iter;
+  float lambda_init, cost_thresh, dist_thresh;
+  int32_t *pix;    // [B, N, 2] out: (u, v)
+  uint8_t *valid;  // [B, N] out: converged && not occluded
+  int32_t *n_valid;  // [B] zeroed
+};
+
+__global__ void __launch_bounds__(kMatchThreads) match_proj_kernel(MatchProjArgs A) {
+  if (blockIdx.x == 0)
+    for (int64_t k = threadIdx.x; k < A.B; k += kMatchThreads) A.n_valid[k] = 0;
+  const int64_t gid = (int64_t)blockIdx.x * kMatchThreads + threadIdx.x;
+  if (gid >= A.B * A.N) return;
+  const int64_t b = gid / A.N;
+  int64_t lin = gid - b * A.N;
+  if (A.idx_init) lin = A.idx_init[gid];
+  int64_t u0 = lin % A.W;
+  if (u0 < 0) u0 += A.W;
+  const int64_t v0 = (lin - u0) / A.W;
+  const float *img = A.rays_img + b * A.H * A.W * 9;
+  const float W2 = (float)(A.W - 2), H2 = (float)(A.H - 2);
+  float u = clampf((float)u0, 1.0f, W2);
+  float v = clampf((float)v0, 1.0f, H2);
+  const float p[3] = {A.pts_norm[3 * gid], A.pts_norm[3 * gid + 1], A.pts_norm[3 * gid + 2]};
+  const bool conv = lm_project(img, A.W, W2, H2, p, A.max_iter, A.lambda_init, A.cost_thresh, u, v);
+  const int pu = (int)u, pv = (int)v;
+  const float *x1 = A.X11 + ((b * A.H + pv) * A.W + pu) * 3;
+  const float *x2 = A.X21 + 3 * gid;
+  const float dx = x1[0] - x2[0], dy = x1[1] - x2[1], dz = x1[2] - x2[2];
+  const float d2 = dx * dx + dy * dy + dz * dz;
+  A.pix[2 * gid] = pu;
+  A.pix[2 * gid + 1] = pv;
+  A.valid[gid] = (conv && sqrtf(d2) < A.dist_thresh) ? 1 : 0;
 }
 
 #pragma clang fp contract(on)
@@ -173,8 +231,69 @@ __device__ __forceinline__ _Float16 score_step(_Float16 a, _Float16 b, _Float16 
 // planes 305 us. Neighbouring lanes here score neighbouring queries, so one
 // load instruction reads the same few D11 lines for the whole wave and a
 // candidate's 48 B sit in one line: the L1 serves it; each variant lost that.
-template <typename T, int FMAX>
-__global__ void __launch_bounds__(kMatchThreads) refine_kernel(m3s_refine_args A) {
+//
+// Both refine kernels are templates on a policy IO that says where the centre
+// comes from and where the result goes (the scan between the two is one
+// definition):
+// * RefineIO, the ABI's m3s_refine_matches: int64 (u, v) pairs in and out,
+//   read and written by the kernels' own statements. An empty parameter the
+//   kernels never touch: these instantiations compile to the instructions
+//   they had before the policy existed (compared on the gfx950 assembly);
+// * RefineDenseIO, the second half of m3s_match_dense: the int32 pixel pair
+//   of match_proj_kernel in; out, in the caller's rows (batch b at
+//   base + b * stride elements), idx = u + W v (matching.py:88), the valid
+//   byte, Q = sqrt(Q11[b, idx] * Q21[b, n]) (global_opt.py:56,
+//   tracker.py:41: one fp32 multiply, one correctly rounded square root) and,
+//   per batch element, the count of valid && Q > Q_conf. The count is a wave
+//   ballot per batch element the wave holds (two when N is no multiple of
+//   64, eight when N = 9) and one integer atomic add per wave and element:
+//   integer sums have no order, so the count is deterministic. Lanes past
+//   B*N have left before the store: wave operations only, no block-wide
+//   barrier.
+struct RefineIO {
+  static constexpr bool kDense = false;
+};
+
+struct RefineDenseIO {  // beside an m3s_refine_args with N = H * W (p1 / p1_new unused)
+  static constexpr bool kDense = true;
+  const int32_t *pix;       // [B, N, 2]
+  const uint8_t *valid_in;  // [B, N]
+  const float *Q11, *Q21;   // [B, N]
+  int32_t *idx;
+  uint8_t *valid;
+  float *Q;
+  int64_t idx_stride, valid_stride, Q_stride;  // elements between batch rows
+  float Q_conf;
+  int32_t *n_valid;  // [B], zeroed by match_proj_kernel
+  __device__ __forceinline__ void centre(int64_t gid, int64_t &u, int64_t &v) const {
+    u = pix[2 * gid], v = pix[2 * gid + 1];
+  }
+  __device__ __forceinline__ void store(int64_t B, int64_t N, int64_t W, int64_t gid, int64_t b, int64_t u,
+                                        int64_t v) const {
+#pragma clang fp contract(off)
+    const int64_t n = gid - b * N;
+    const int32_t lin = (int32_t)(u + W * v);
+    const float q = sqrtf(Q11[b * N + lin] * Q21[gid]);
+    const uint8_t ok = valid_in[gid];
+    idx[b * idx_stride + n] = lin;
+    valid[b * valid_stride + n] = ok;
+    Q[b * Q_stride + n] = q;
+    // every lane of the wave that is still here takes part; the wave's lanes
+    // are consecutive gids, so its batch elements are the range [b0, b1]
+    const bool counted = ok != 0 && q > Q_conf;
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t g0 = gid - lane, BN = B * N;
+    const int64_t g1 = g0 + 63 < BN ? g0 + 63 : BN - 1;
+    const int64_t b1 = g1 / N;
+    for (int64_t bb = g0 / N; bb <= b1; bb++) {
+      const uint64_t m = __builtin_amdgcn_ballot_w64(counted && b == bb);
+      if (lane == 0 && m != 0) atomicAdd(&n_valid[bb], (int)__builtin_popcountll(m));
+    }
+  }
+};
+
+template <typename T, int FMAX, class IO>
+__global__ void __launch_bounds__(kMatchThreads) refine_kernel(m3s_refine_args A, IO io) {
   const int64_t gid = (int64_t)blockIdx.x * kMatchThreads + threadIdx.x;
   if (gid >= A.B * A.N) return;
   const int64_t b = gid / A.N;
@@ -186,7 +305,9 @@ __global__ void __launch_bounds__(kMatchThreads) refine_kernel(m3s_refine_args A
 #pragma unroll
     for (int k = 0; k < FMAX; k++) q[k] = d21[k];
   }
-  int64_t u0 = A.p1[2 * gid], v0 = A.p1[2 * gid + 1];
+  int64_t u0, v0;
+  if constexpr (IO::kDense) io.centre(gid, u0, v0);
+  else u0 = A.p1[2 * gid], v0 = A.p1[2 * gid + 1];
   T max_score = score_start<T>();
   int64_t u_new = u0, v_new = v0;
   for (int d = A.dilation_max; d > 0; d--) {
@@ -216,8 +337,12 @@ __global__ void __launch_bounds__(kMatchThreads) refine_kernel(m3s_refine_args A
     u0 = u_new;
     v0 = v_new;
   }
-  A.p1_new[2 * gid] = u_new;
-  A.p1_new[2 * gid + 1] = v_new;
+  if constexpr (IO::kDense) {
+    io.store(A.B, A.N, A.W, gid, b, u_new, v_new);
+  } else {
+    A.p1_new[2 * gid] = u_new;
+    A.p1_new[2 * gid + 1] = v_new;
+  }
 }
 
 // ---- round 5: refine_f16_kernel (fp16 descriptors, F in {16, 24, 32}) ----
@@ -279,8 +404,8 @@ __device__ __forceinline__ void score2_f16(const h2v (&q)[4 * NL], const u32x4m 
   sa = a, sb = b;
 }
 
-template <int FMAX, int NR>
-__global__ void __launch_bounds__(kMatchThreads) refine_f16_kernel(m3s_refine_args A, int per_xcd) {
+template <int FMAX, int NR, class IO>
+__global__ void __launch_bounds__(kMatchThreads) refine_f16_kernel(m3s_refine_args A, int per_xcd, IO io) {
   constexpr int NL = FMAX / 8;  // 16-B loads per descriptor
   constexpr int N1 = 2 * NR + 1, NN = N1 * N1;
   constexpr int F2 = FMAX * 2;  // bytes per descriptor
@@ -305,7 +430,9 @@ __global__ void __launch_bounds__(kMatchThreads) refine_f16_kernel(m3s_refine_ar
       for (int k = 0; k < 4; k++) q[4 * l + k] = __builtin_bit_cast(h2v, (unsigned)v[k]);
     }
   }
-  const int64_t pu = A.p1[2 * gid], pv = A.p1[2 * gid + 1];
+  int64_t pu, pv;
+  if constexpr (IO::kDense) io.centre(gid, pu, pv);
+  else pu = A.p1[2 * gid], pv = A.p1[2 * gid + 1];
   // a centre this far out has no candidate inside the image at any dilation
   // (radius * dilation_max < 2^20): the reference returns it unchanged
   const bool far = pu < -(1 << 30) || pu > (1 << 30) || pv < -(1 << 30) || pv > (1 << 30);
@@ -378,15 +505,19 @@ __global__ void __launch_bounds__(kMatchThreads) refine_f16_kernel(m3s_refine_ar
       v0 = vb + (best % N1) * d;
     }
   }
-  A.p1_new[2 * gid] = moved ? (int64_t)u0 : pu;
-  A.p1_new[2 * gid + 1] = moved ? (int64_t)v0 : pv;
+  if constexpr (IO::kDense) {
+    io.store(A.B, A.N, A.W, gid, b, moved ? (int64_t)u0 : pu, moved ? (int64_t)v0 : pv);
+  } else {
+    A.p1_new[2 * gid] = moved ? (int64_t)u0 : pu;
+    A.p1_new[2 * gid + 1] = moved ? (int64_t)v0 : pv;
+  }
 }
 
 #ifndef M3S_REF_V2
 #define M3S_REF_V2 1
 #endif
-template <typename T>
-int launch_refine(const m3s_refine_args &a, hipStream_t st) {
+template <typename T, class IO>
+int launch_refine(const m3s_refine_args &a, const IO &io, hipStream_t st) {
   const unsigned blocks = (unsigned)((a.B * a.N + kMatchThreads - 1) / kMatchThreads);
   if (M3S_REF_V2 && sizeof(T) == 2 && (a.F == 16 || a.F == 24 || a.F == 32) && a.radius == 3 &&
       a.B * a.H * a.W * a.F * 2 < (1ll << 30) && a.dilation_max < (1 << 16) && a.H < (1 << 20) &&
@@ -394,19 +525,35 @@ int launch_refine(const m3s_refine_args &a, hipStream_t st) {
     const int per = (int)((blocks + 7) / 8);
     const unsigned grid = M3S_REF_XCD ? 8u * (unsigned)per : blocks;
     switch (a.F) {
-      case 16: refine_f16_kernel<16, 3><<<grid, kMatchThreads, 0, st>>>(a, per); break;
-      case 24: refine_f16_kernel<24, 3><<<grid, kMatchThreads, 0, st>>>(a, per); break;
-      default: refine_f16_kernel<32, 3><<<grid, kMatchThreads, 0, st>>>(a, per); break;
+      case 16: refine_f16_kernel<16, 3, IO><<<grid, kMatchThreads, 0, st>>>(a, per, io); break;
+      case 24: refine_f16_kernel<24, 3, IO><<<grid, kMatchThreads, 0, st>>>(a, per, io); break;
+      default: refine_f16_kernel<32, 3, IO><<<grid, kMatchThreads, 0, st>>>(a, per, io); break;
     }
     return launch_status();
   }
   switch (a.F) {  // descriptor width in registers for the common sizes
-    case 16: refine_kernel<T, 16><<<blocks, kMatchThreads, 0, st>>>(a); break;
-    case 24: refine_kernel<T, 24><<<blocks, kMatchThreads, 0, st>>>(a); break;
-    case 32: refine_kernel<T, 32><<<blocks, kMatchThreads, 0, st>>>(a); break;
-    default: refine_kernel<T, 0><<<blocks, kMatchThreads, 0, st>>>(a); break;
+    case 16: refine_kernel<T, 16, IO><<<blocks, kMatchThreads, 0, st>>>(a, io); break;
+    case 24: refine_kernel<T, 24, IO><<<blocks, kMatchThreads, 0, st>>>(a, io); break;
+    case 32: refine_kernel<T, 32, IO><<<blocks, kMatchThreads, 0, st>>>(a, io); break;
+    default: refine_kernel<T, 0, IO><<<blocks, kMatchThreads, 0, st>>>(a, io); break;
   }
   return launch_status();
+}
+
+// workspace of m3s_match_dense: byte offsets of its sections (256-B aligned)
+struct DenseLayout {
+  size_t rays, pts, pix, valid, total;
+};
+inline DenseLayout dense_layout(int64_t B, int64_t N) {
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t n = (size_t)B * (size_t)N;
+  DenseLayout L;
+  L.rays = 0;
+  L.pts = up(L.rays + n * 9 * sizeof(float));
+  L.pix = up(L.pts + n * 3 * sizeof(float));
+  L.valid = up(L.pix + n * 2 * sizeof(int32_t));
+  L.total = up(L.valid + n);
+  return L;
 }
 
 }  // namespace
@@ -428,9 +575,56 @@ int m3s_refine_matches(const m3s_refine_args *a, void *stream) {
     return M3S_EINVAL;
   if (a->B * a->N == 0) return M3S_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (a->dtype == M3S_DESC_F16) return launch_refine<_Float16>(*a, st);
-  if (a->dtype == M3S_DESC_F32) return launch_refine<float>(*a, st);
+  if (a->dtype == M3S_DESC_F16) return launch_refine<_Float16>(*a, RefineIO{}, st);
+  if (a->dtype == M3S_DESC_F32) return launch_refine<float>(*a, RefineIO{}, st);
   return M3S_EINVAL;
+}
+
+size_t m3s_match_dense_workspace_size(int64_t B, int64_t H, int64_t W) {
+  if (B < 0 || H < 0 || W < 0) return 0;
+  return dense_layout(B, H * W).total;
+}
+
+int m3s_match_dense(const m3s_match_dense_args *a, void *stream) {
+  if (!a || !a->X11 || !a->X21 || !a->D11 || !a->D21 || !a->Q11 || !a->Q21 || !a->idx || !a->valid || !a->Q ||
+      !a->n_valid || !a->workspace)
+    return M3S_EINVAL;
+  if (a->B < 0 || a->H < 3 || a->W < 3 || a->F < 1 || a->max_iter < 0 || a->radius < 0 || a->dilation_max < 0)
+    return M3S_EINVAL;
+  if (a->dtype != M3S_DESC_F16 && a->dtype != M3S_DESC_F32) return M3S_EINVAL;
+  if (a->H > ((1ll << 31) - 1) / a->W) return M3S_EINVAL;  // idx is int32: H * W < 2^31
+  const int64_t N = a->H * a->W;
+  if (a->idx_stride < N || a->valid_stride < N || a->Q_stride < N) return M3S_EINVAL;
+  const DenseLayout L = dense_layout(a->B, N);
+  if (a->workspace_bytes < L.total) return M3S_EINVAL;
+  if (a->B == 0) return M3S_OK;
+  char *ws = static_cast<char *>(a->workspace);
+  float *rays = reinterpret_cast<float *>(ws + L.rays), *pts = reinterpret_cast<float *>(ws + L.pts);
+  int32_t *pix = reinterpret_cast<int32_t *>(ws + L.pix);
+  uint8_t *ok = reinterpret_cast<uint8_t *>(ws + L.valid);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // 1: ray image with gradients + unit rays (m3s_fuse.hip)
+  const m3s_prep_rays_args pa{a->X11, a->X21, a->B, a->H, a->W, rays, pts};
+  int rc = m3s_prep_rays(&pa, stream);
+  if (rc != M3S_OK) return rc;
+  // 2: projection + occlusion test (+ n_valid <- 0)
+  const MatchProjArgs ja{rays, pts, a->X11, a->X21, a->idx_init, a->B, a->H, a->W, N, a->max_iter,
+                         a->lambda_init, a->cost_thresh, a->dist_thresh, pix, ok, a->n_valid};
+  const unsigned blocks = (unsigned)((a->B * N + kMatchThreads - 1) / kMatchThreads);
+  match_proj_kernel<<<blocks, kMatchThreads, 0, st>>>(ja);
+  if ((rc = launch_status()) != M3S_OK) return rc;
+  // 3: refinement + finalize. radius 0: the reference skips refine_matches
+  // (matching.py:77); no dilation level runs and the pixel stays.
+  m3s_refine_args ra{};
+  ra.D11 = a->D11, ra.D21 = a->D21;
+  ra.B = a->B, ra.H = a->H, ra.W = a->W, ra.N = N, ra.F = a->F;
+  ra.dtype = a->dtype, ra.radius = a->radius, ra.dilation_max = a->radius > 0 ? a->dilation_max : 0;
+  RefineDenseIO io{};
+  io.pix = pix, io.valid_in = ok, io.Q11 = a->Q11, io.Q21 = a->Q21;
+  io.idx = a->idx, io.valid = a->valid, io.Q = a->Q;
+  io.idx_stride = a->idx_stride, io.valid_stride = a->valid_stride, io.Q_stride = a->Q_stride;
+  io.Q_conf = a->Q_conf, io.n_valid = a->n_valid;
+  return a->dtype == M3S_DESC_F16 ? launch_refine<_Float16>(ra, io, st) : launch_refine<float>(ra, io, st);
 }
 
 }  // extern "C"

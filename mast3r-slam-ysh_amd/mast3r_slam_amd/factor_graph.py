@@ -26,13 +26,18 @@ X / C keep the SharedKeyframes array-of-structs layout [cap, HW, 3]: the GN
 gathers X_i through idx, and one 12-B point per gathered pixel stays within
 one cache line (three separate planes would touch three). ``add_factors`` takes the outputs of
 mast3r_match_symmetric (the network is out of scope) and applies the
-reference's edge filter (global_opt.py:56-78).
+reference's edge filter (global_opt.py:56-78); ``add_factors_dense`` takes the
+decoder's outputs instead and runs matching, the quality combine and the same
+filter with the results written straight into the edge store.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 import mast3r_slam_backends as be
+
+from .matching import MATCHING_CFG, match_dense
 
 # config/base.yaml:35-50
 LOCAL_OPT_CFG = dict(pin=1, window_size=1e6, C_conf=0.0, Q_conf=1.5, min_match_frac=0.1,
@@ -74,6 +79,12 @@ class EdgeStore:
         self._valid[r0 + 1:r1:2] = valid_i.reshape(e, -1, 1)
         self._Q[r0:r1:2], self._Q[r0 + 1:r1:2] = Qj.reshape(e, -1, 1), Qi.reshape(e, -1, 1)
         self.n += e
+
+    def reserve(self, e):
+        """Capacity for e more undirected edges; returns their first row 2n."""
+        if self.n + e > self.capacity:
+            self._alloc(max(2 * self.capacity, self.n + e))
+        return 2 * self.n
 
     def directed(self):
         """Views (ii, jj, idx_ii2jj, valid_match, Q) of the 2n directed edges."""
@@ -169,6 +180,60 @@ class FactorGraph:
                           valid_match_i[keep], Qj[keep], Qi[keep])
         self.ii_u = torch.cat([self.ii_u, ii[keep]])
         self.jj_u = torch.cat([self.jj_u, jj[keep]])
+        return True
+
+    def add_factors_dense(self, ii, jj, Xii, Xji, Xjj, Xij, Dii, Dji, Djj, Dij, Qii, Qji, Qjj, Qij,
+                          min_match_frac, is_reloc=False, match_cfg=MATCHING_CFG):
+        """global_opt.py:31-100 from the decoder's outputs (the tensors of
+        mast3r_match_symmetric, mast3r_utils.py:150-152: X.. [e,h,w,3], D..
+        [e,h,w,F], Q.. [e,h,w]): matching, quality combine, match fractions and
+        the edge filter, without the torch glue between them.
+
+        The symmetric batch of mast3r_utils.py:155-158 is matched as its two
+        halves, (Xii, Xji, ..) and (Xjj, Xij, ..), so no input is concatenated:
+        ``matching.match_dense`` writes idx / valid_match / Q of the i->j half
+        into rows 2n, 2n+2, .. of the edge store and of the j->i half into rows
+        2n+1, 2n+3, .. (six launches in all). The 2e counts of
+        valid_match & (Q > Q_conf) come back in one host read (the reference's
+        one sync, ``invalid_edges.any()``); the filter runs on the host, and
+        the kept rows are compacted in place only when an edge was rejected.
+        ii / jj are host sequences as in the reference (device tensors cost a
+        second read). The stored ``valid`` is valid_match, as in the reference:
+        the GN applies Q_conf itself. Returns what add_factors returns."""
+        ii_h = ii.tolist() if isinstance(ii, torch.Tensor) else [int(k) for k in ii]
+        jj_h = jj.tolist() if isinstance(jj, torch.Tensor) else [int(k) for k in jj]
+        e, st, dev = len(ii_h), self.edges, self.frames.device
+        if e == 0:
+            return False
+        r0 = st.reserve(e)
+        r1 = r0 + 2 * e
+        counts = torch.empty(2 * e, dtype=torch.int32, device=dev)
+        for k, (X11, X21, D11, D21, Q11, Q21) in enumerate(((Xii, Xji, Dii, Dji, Qii, Qji),
+                                                            (Xjj, Xij, Djj, Dij, Qjj, Qij))):
+            rows = slice(r0 + k, r1, 2)
+            match_dense(X11, X21, D11, D21, Q11, Q21, cfg=match_cfg, Q_conf=self.cfg["Q_conf"],
+                        out=(st._idx[rows], st._valid[rows], st._Q[rows], counts[k * e:(k + 1) * e]))
+        # global_opt.py:63-74 in its float32: sum / n, minimum, < min_match_frac
+        frac = counts.cpu().numpy().astype("float32") / np.float32(st.HW)
+        keep = [bool(not min(frac[k], frac[e + k]) < np.float32(min_match_frac) or ii_h[k] == jj_h[k] - 1)
+                for k in range(e)]
+        if not all(keep) and is_reloc:
+            return False
+        kept = [k for k in range(e) if keep[k]]
+        if not kept:
+            return False
+        if len(kept) < e:
+            src = torch.as_tensor([r0 + 2 * k + d for k in kept for d in (0, 1)], device=dev)
+            for buf in (st._idx, st._valid, st._Q):
+                buf[r0:r0 + 2 * len(kept)] = buf[src]
+        ii_k = torch.as_tensor([ii_h[k] for k in kept], dtype=torch.int64, device=dev)
+        jj_k = torch.as_tensor([jj_h[k] for k in kept], dtype=torch.int64, device=dev)
+        r1 = r0 + 2 * len(kept)
+        st._ii[r0:r1:2], st._ii[r0 + 1:r1:2] = ii_k, jj_k
+        st._jj[r0:r1:2], st._jj[r0 + 1:r1:2] = jj_k, ii_k
+        st.n += len(kept)
+        self.ii_u = torch.cat([self.ii_u, ii_k])
+        self.jj_u = torch.cat([self.jj_u, jj_k])
         return True
 
     def get_unique_kf_idx(self):

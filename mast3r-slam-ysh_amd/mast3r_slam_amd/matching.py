@@ -62,3 +62,23 @@ def match_iterative_proj(X11, X21, D11, D21, idx_1_to_2_init=None, cfg=MATCHING_
 def match(X11, X21, D11, D21, idx_1_to_2_init=None, cfg=MATCHING_CFG):
     """matching.py:8-10."""
     return match_iterative_proj(X11, X21, D11, D21, idx_1_to_2_init, cfg)
+
+
+def match_dense(X11, X21, D11, D21, Q11, Q21, idx_1_to_2_init=None, cfg=MATCHING_CFG, Q_conf=1.5, out=None):
+    """``match`` and what its callers do next, fused (three launches, no torch
+    glue; mast3r_slam_backends.match_dense): -> (idx int32 [b,hw], valid
+    [b,hw,1] bool, Q = sqrt(Q11[b, idx] * Q21) [b,hw,1], n_valid int32 [b], the
+    count of valid & (Q > Q_conf)).
+
+    For the factor graph (global_opt.py:40-66) these are one direction's
+    idx / valid_match / Q and match_frac * hw; FactorGraph.add_factors_dense
+    has them written straight into its edge store through ``out``. For the
+    tracker, with X11 / D11 / Q11 = Xff / Dff / Qff (the frame in its own
+    camera), X21 / D21 / Q21 = Xkf / Dkf / Qkf (the keyframe's pixels seen from
+    the frame; mast3r_match_asymmetric) and idx_1_to_2_init the previous
+    idx_f2k, they are idx_f2k, valid_match_k and Qk of tracker.py:31-41. Q_conf defaults to base.yaml's local_opt.Q_conf
+    (tracking.Q_conf has the same value)."""
+    return be.match_dense(X11, X21, D11, D21, Q11, Q21, idx_1_to_2_init, max_iter=cfg["max_iter"],
+                          lambda_init=cfg["lambda_init"], convergence_thresh=cfg["convergence_thresh"],
+                          dist_thresh=cfg["dist_thresh"], radius=cfg["radius"],
+                          dilation_max=cfg["dilation_max"], Q_conf=Q_conf, out=out)
