@@ -164,6 +164,78 @@ size_t m3s_track_workspace_size(int64_t HW);
 int m3s_track_rays_sim3(const m3s_track_args *a, void *stream);
 int m3s_track_calib_sim3(const m3s_track_args *a, void *stream);
 
+/* ---- tracker front end (new entry point): FrameTracker.track between the
+ *      matching and the fusion (tracker.py:41-67, 103-108, 129-154) ----
+ * From the canonical pointmaps of the frame and the keyframe and the rows
+ * m3s_match_dense wrote (idx_f2k, valid_match_k, Qk), three small launches
+ * form, for every keyframe pixel n with j = idx_f2k[n]:
+ *   Xf_g[n]      Xf_canon[j]; calib: (z (u - cx) / fx, z (v - cy) / fy, z) with
+ *                z = Xf_canon[j].z, u = j % W, v = j / W (constrain_points_to_ray,
+ *                geometry.py:37-42: divide first, then multiply)
+ *   Xk_g[n]      the same rule on Xk_canon[n] at pixel n (rays: Xk_canon itself)
+ *   valid_opt[n] valid_match[n] && Cf_sum[j] / Nf > C_conf &&
+ *                Ck_sum[n] / Nk > C_conf && Qk[n] > Q_conf (fp32 divisions)
+ *   stats[0]     n_opt:    count of valid_opt                  (tracker.py:67)
+ *   stats[1]     n_kf:     count of valid_match && Qk > Q_conf (:65, :104)
+ *   stats[2]     n_unique: distinct j over pixels with valid_match (:106-108),
+ *                counted in a byte map of the frame's pixels; nothing is sorted
+ *   stats[3]     reserved, written as 0
+ * and then exactly the launches of m3s_track_rays_sim3 (K == NULL) or
+ * m3s_track_calib_sim3 on (Xf_g, Xk_g, Qk, valid_opt). The counts are exact
+ * integers; the map and the counters are cleared inside every call.
+ *   Xf_canon, Xk_canon float [HW,3]; Cf_sum, Ck_sum float [HW] (the summed
+ *   confidences Frame.C) with their update counts Nf, Nk >= 1 (Frame.N);
+ *   idx_f2k int32 [HW], every entry in [0, HW) (the caller's contract: the
+ *   call does not scan for it); valid_match uint8 [HW]; Qk float [HW];
+ *   T_WCf, T_WCk [8]; K device float [3,3] or NULL; height * width == HW.
+ * Outputs: T_WCf_out, T_CkCf_out, info as in m3s_track_args; stats int32 [4]
+ * device. Xf_out [HW,3], Xk_out [HW,3], valid_opt_out [HW] are optional: NULL
+ * keeps the prepared rows in the workspace. In rays mode the keyframe rows
+ * are a plain copy, made only into a non-NULL Xk_out other than Xk_canon.
+ * No allocation; host synchronisation only as the tracker entry points have
+ * it (sync_every; calib: their one read of K before the tracker launches). */
+typedef struct m3s_track_frame_args {
+  const float *Xf_canon;
+  const float *Cf_sum;
+  const float *Xk_canon;
+  const float *Ck_sum;
+  const int32_t *idx_f2k;
+  const uint8_t *valid_match;
+  const float *Qk;
+  const float *T_WCf;
+  const float *T_WCk;
+  const float *K; /* NULL: rays mode */
+  int64_t HW;
+  int32_t Nf, Nk;
+  int height, width;
+  float C_conf, Q_conf; /* config tracking.C_conf, tracking.Q_conf */
+  /* the optimisation parameters of m3s_track_args */
+  int pixel_border;
+  float z_eps;
+  float sigma_a, sigma_b;
+  float huber_k;
+  int max_iters;
+  float rel_error, delta_norm;
+  int sync_every;
+  float *T_WCf_out;
+  float *T_CkCf_out;
+  int32_t *info;
+  int32_t *stats;
+  float *Xf_out;          /* optional */
+  float *Xk_out;          /* optional */
+  uint8_t *valid_opt_out; /* optional */
+  void *workspace;
+  size_t workspace_bytes;
+} m3s_track_frame_args;
+
+#define M3S_STAT_N_OPT 0
+#define M3S_STAT_N_KF 1
+#define M3S_STAT_N_UNIQUE 2
+
+/* the tracker workspace, the map (HW bytes) and the prepared rows */
+size_t m3s_track_frame_workspace_size(int64_t HW);
+int m3s_track_frame(const m3s_track_frame_args *a, void *stream);
+
 /* build identification (for the loaded-library check) */
 const char *m3s_version(void);
 

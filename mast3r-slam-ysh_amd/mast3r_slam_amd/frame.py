@@ -4,7 +4,7 @@ tracker's fusion step (tracker.py:98-99), with the per-pixel work in the HIP
 kernel ``mast3r_slam_backends.fuse_pointmap``.
 
 ``Pointmap`` holds what the reference ``Frame`` holds for this purpose
-(X_canon [HW,3], C [HW,1], N, N_updates, score) and applies the same
+(X_canon [HW,3], C [HW,1], N, N_updates, score, and the pose T_WC) and applies the same
 filtering modes (config tracking.filtering_mode). weighted_pointmap (the
 default), weighted_spherical, indep_conf and recent run in one fused device
 pass; first and best_score are whole-tensor copies decided on the host as the
@@ -26,6 +26,7 @@ class Pointmap:
         self.N = 0
         self.N_updates = 0
         self.score = None
+        self.T_WC = None  # Sim3 [1], the pose Frame.T_WC holds (read and set by tracker.FrameTracker)
 
     def get_score(self, C):  # frame.py:33-39
         return torch.median(C) if self.filtering_score == "median" else torch.mean(C)

@@ -15,7 +15,10 @@ raise ``RuntimeError`` — there is no CPU fallback: without the HIP library thi
 module fails at import.
 
 New entry points (the reference tracker has no backend call, tracker.py:173-266):
-``track_rays_sim3`` and ``track_calib_sim3``.
+``track_rays_sim3`` and ``track_calib_sim3``, and ``track_frame``: the rest of
+FrameTracker.track between the matching and the fusion (gathers, the calib ray
+constraint, valid_opt, the three counts of the skip / new-keyframe decisions)
+in three launches in front of the same tracker launches.
 
 ``iter_proj`` / ``refine_matches`` (gn.cpp:84-114, matching_kernels.cu) run
 the HIP matching kernels with the reference's signatures and return values.
@@ -136,6 +139,27 @@ class TrackArgs(ctypes.Structure):
     ]
 
 
+class TrackFrameArgs(ctypes.Structure):
+    """Mirror of ``m3s_track_frame_args`` (include/m3s_gn.h)."""
+
+    _fields_ = [
+        ("Xf_canon", _VP), ("Cf_sum", _VP), ("Xk_canon", _VP), ("Ck_sum", _VP),
+        ("idx_f2k", _VP), ("valid_match", _VP), ("Qk", _VP), ("T_WCf", _VP), ("T_WCk", _VP), ("K", _VP),
+        ("HW", ctypes.c_int64), ("Nf", ctypes.c_int32), ("Nk", ctypes.c_int32),
+        ("height", ctypes.c_int), ("width", ctypes.c_int),
+        ("C_conf", ctypes.c_float), ("Q_conf", ctypes.c_float),
+        ("pixel_border", ctypes.c_int), ("z_eps", ctypes.c_float),
+        ("sigma_a", ctypes.c_float), ("sigma_b", ctypes.c_float), ("huber_k", ctypes.c_float),
+        ("max_iters", ctypes.c_int), ("rel_error", ctypes.c_float), ("delta_norm", ctypes.c_float),
+        ("sync_every", ctypes.c_int),
+        ("T_WCf_out", _VP), ("T_CkCf_out", _VP), ("info", _VP), ("stats", _VP),
+        ("Xf_out", _VP), ("Xk_out", _VP), ("valid_opt_out", _VP),
+        ("workspace", _VP), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+STAT_N_OPT, STAT_N_KF, STAT_N_UNIQUE = 0, 1, 2
+
 # every symbol include/m3s_gn.h declares
 EXPORTS = (
     "m3s_gn_workspace_size", "m3s_gauss_newton_points", "m3s_gauss_newton_rays",
@@ -145,6 +169,7 @@ EXPORTS = (
     "m3s_fuse_pointmap", "m3s_prep_rays", "m3s_debug_stamps", "m3s_debug_sim3",
     "m3s_debug_copy", "m3s_set_knob", "m3s_debug_call_timing", "m3s_debug_call_times",
     "m3s_match_dense_workspace_size", "m3s_match_dense",
+    "m3s_track_frame_workspace_size", "m3s_track_frame",
 )
 FILTER_MODES = {"weighted_pointmap": 0, "indep_conf": 1, "recent": 2, "weighted_spherical": 3}
 
@@ -174,6 +199,10 @@ def _load(path=LIB_PATH):
     for f in ("m3s_track_rays_sim3", "m3s_track_calib_sim3"):
         getattr(lib, f).restype = ctypes.c_int
         getattr(lib, f).argtypes = [P(TrackArgs), _VP]
+    lib.m3s_track_frame_workspace_size.restype = ctypes.c_size_t
+    lib.m3s_track_frame_workspace_size.argtypes = [ctypes.c_int64]
+    lib.m3s_track_frame.restype = ctypes.c_int
+    lib.m3s_track_frame.argtypes = [P(TrackFrameArgs), _VP]
     lib.m3s_version.restype = ctypes.c_char_p
     lib.m3s_version.argtypes = []
     lib.m3s_sparse_plan_debug.restype = ctypes.c_int64
@@ -764,6 +793,112 @@ def track_calib_sim3(Xf, Xk, T_WCf, T_WCk, Qk, valid, K, img_size, sigma_pixel, 
     return _track("m3s_track_calib_sim3", Xf, Xk, T_WCf, T_WCk, Qk, valid, K, img_size,
                   sigma_pixel, sigma_depth, huber_k, max_iters, rel_error, delta_norm,
                   pixel_border=pixel_border, z_eps=z_eps, sync_every=sync_every, workspace=workspace)
+
+
+def track_frame_workspace_size(HW):
+    """Bytes of the track_frame workspace for an image of HW pixels."""
+    return int(_lib.m3s_track_frame_workspace_size(int(HW)))
+
+
+def track_frame(Xf_canon, Cf_sum, Nf, Xk_canon, Ck_sum, Nk, idx_f2k, valid_match, Qk, T_WCf, T_WCk,
+                K, img_size, C_conf, Q_conf, sigma_a, sigma_b, huber_k, max_iters, rel_error,
+                delta_norm, pixel_border=0, z_eps=0.0, sync_every=0, workspace=None,
+                return_prepared=False, out=None):
+    """FrameTracker.track from the matches to the refined pose on the device
+    (new entry point; m3s_track_frame): get_points_poses (tracker.py:129-154),
+    valid_opt / valid_kf (:60-65) and the three counts behind match_frac,
+    match_frac_k and unique_frac_f (:67, :104-108) in three launches, then the
+    launches of track_rays_sim3 (K is None) or track_calib_sim3 on the result.
+
+    Xf_canon, Xk_canon [HW,3] f32; Cf_sum, Ck_sum [HW(,1)] f32, the summed
+    confidences (Pointmap.C) with their update counts Nf, Nk (Pointmap.N);
+    idx_f2k [HW] (or [1,HW]) int32 as match_dense writes it, every entry in
+    [0, HW) -- not scanned; valid_match [HW(,1)] bool; Qk [HW(,1)] f32; T_WCf,
+    T_WCk [8] or [1,8]; K [3,3] f32 or None (rays mode); img_size (H, W) with
+    H * W == HW; sigma_a / sigma_b as track_rays_sim3 (rays) or
+    track_calib_sim3 (calib) name them.
+
+    -> (T_WCf [1,8], T_CkCf [1,8], info int32[8], stats int32[4]) with stats =
+    (n_opt, n_kf, n_unique, 0); with return_prepared=True also (Xf_g [HW,3],
+    Xk_g [HW,3], valid_opt [HW,1] bool), the rows the tracker launches read.
+    out: an int32 [12] device tensor; info and stats are then its views [:8]
+    and [8:], so that one copy brings both to the host. No host
+    synchronisation here (calib mode: the tracker entry point's one read of K)."""
+    _check(Xf_canon, "Xf_canon", torch.float32)
+    _check(Cf_sum, "Cf_sum", torch.float32)
+    _check(Xk_canon, "Xk_canon", torch.float32)
+    _check(Ck_sum, "Ck_sum", torch.float32)
+    _check(idx_f2k, "idx_f2k", torch.int32)
+    _check(valid_match, "valid_match", torch.bool)
+    _check(Qk, "Qk", torch.float32)
+    T_WCf = T_WCf.contiguous()
+    T_WCk = T_WCk.contiguous()
+    _check(T_WCf, "T_WCf", torch.float32)
+    _check(T_WCk, "T_WCk", torch.float32)
+    if K is not None:
+        _check(K, "K", torch.float32)
+        if K.numel() != 9:
+            raise RuntimeError("track_frame: K must be [3,3]")
+    if T_WCf.numel() != 8 or T_WCk.numel() != 8:
+        raise RuntimeError("track_frame: T_WCf / T_WCk must be [8] or [1,8]")
+    HW = int(Xk_canon.shape[0])
+    H, W = int(img_size[0]), int(img_size[1])
+    if H < 1 or W < 1 or H * W != HW:
+        raise RuntimeError(f"track_frame: img_size {H} x {W} does not hold HW = {HW} pixels")
+    if Xf_canon.numel() != 3 * HW or Xk_canon.numel() != 3 * HW:
+        raise RuntimeError("track_frame: Xf_canon / Xk_canon must be [HW,3]")
+    for name, t in (("Cf_sum", Cf_sum), ("Ck_sum", Ck_sum), ("idx_f2k", idx_f2k),
+                    ("valid_match", valid_match), ("Qk", Qk)):
+        if t.numel() != HW:
+            raise RuntimeError(f"track_frame: {name} must hold HW = {HW} elements (got {tuple(t.shape)})")
+    Nf, Nk = int(Nf), int(Nk)
+    if Nf < 1 or Nk < 1:
+        raise RuntimeError("track_frame: Nf and Nk must be >= 1 (an initialised pointmap)")
+    dev = Xk_canon.device
+    for name, t in (("Xf_canon", Xf_canon), ("Cf_sum", Cf_sum), ("Ck_sum", Ck_sum), ("idx_f2k", idx_f2k),
+                    ("valid_match", valid_match), ("Qk", Qk), ("T_WCf", T_WCf), ("T_WCk", T_WCk), ("K", K)):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"track_frame: {name} is on {t.device}, Xk_canon on {dev}")
+    if out is None:
+        out = torch.empty(12, dtype=torch.int32, device=dev)  # written by the call's first launches
+    else:
+        _check(out, "out", torch.int32)
+        if out.numel() != 12 or out.device != dev:
+            raise RuntimeError(f"track_frame: out must be an int32 [12] tensor on {dev}")
+    info, stats = out.view(-1)[:8], out.view(-1)[8:]
+    out_f = torch.empty(1, 8, dtype=torch.float32, device=dev)
+    out_r = torch.empty(1, 8, dtype=torch.float32, device=dev)
+    need = track_frame_workspace_size(HW)
+    if workspace is None:
+        ws = _workspace(need, dev)
+    else:  # caller-owned (tests: reused / poisoned workspaces)
+        _check(workspace, "workspace", torch.uint8)
+        if workspace.device != dev or workspace.numel() < need:
+            raise RuntimeError(f"track_frame workspace must be a uint8 tensor of >= {need} bytes on {dev}")
+        ws = workspace
+    Xf_g = Xk_g = valid_opt = None
+    if return_prepared:
+        Xf_g = torch.empty(HW, 3, dtype=torch.float32, device=dev)
+        Xk_g = torch.empty(HW, 3, dtype=torch.float32, device=dev)
+        valid_opt = torch.empty(HW, 1, dtype=torch.bool, device=dev)
+    a = TrackFrameArgs()
+    a.Xf_canon, a.Cf_sum, a.Xk_canon, a.Ck_sum = _p(Xf_canon), _p(Cf_sum), _p(Xk_canon), _p(Ck_sum)
+    a.idx_f2k, a.valid_match, a.Qk = _p(idx_f2k), _p(valid_match), _p(Qk)
+    a.T_WCf, a.T_WCk, a.K = _p(T_WCf), _p(T_WCk), _p(K)
+    a.HW, a.Nf, a.Nk, a.height, a.width = HW, Nf, Nk, H, W
+    a.C_conf, a.Q_conf = float(C_conf), float(Q_conf)
+    a.pixel_border, a.z_eps = int(pixel_border), float(z_eps)
+    a.sigma_a, a.sigma_b, a.huber_k = float(sigma_a), float(sigma_b), float(huber_k)
+    a.max_iters, a.rel_error, a.delta_norm = int(max_iters), float(rel_error), float(delta_norm)
+    a.sync_every = int(sync_every)
+    a.T_WCf_out, a.T_CkCf_out, a.info, a.stats = _p(out_f), _p(out_r), _p(info), _p(stats)
+    a.Xf_out, a.Xk_out, a.valid_opt_out = _p(Xf_g), _p(Xk_g), _p(valid_opt)
+    a.workspace, a.workspace_bytes = _p(ws), ws.numel()
+    _raise(_lib.m3s_track_frame(ctypes.byref(a), _stream(dev)), "m3s_track_frame")
+    del ws  # stream-ordered by the caching allocator
+    if return_prepared:
+        return out_f, out_r, info, stats, Xf_g, Xk_g, valid_opt
+    return out_f, out_r, info, stats
 
 
 # -------------------------------------------------- stepwise (sharded) ---
