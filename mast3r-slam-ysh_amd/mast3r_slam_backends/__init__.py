@@ -25,6 +25,11 @@ the HIP matching kernels with the reference's signatures and return values.
 ``match_dense`` (new) is the whole of matching.py:52-90 plus the caller's
 quality combine and match count, from the network's outputs to the rows the
 GN entry points, the edge store and the trackers consume, in three launches.
+
+``asmk_*`` (new; include/m3s_retrieval.h) are the ASMK retrieval steps the
+reference runs on the host after its torch quantize: aggregate (residual sums,
+binarise, pack), search (Hamming similarity, scores, top-k) and append, on an
+``AsmkHandle``; ``mast3r_slam_amd.retrieval.RetrievalDatabase`` is built on them.
 """
 from __future__ import annotations
 
@@ -173,6 +178,54 @@ EXPORTS = (
 )
 FILTER_MODES = {"weighted_pointmap": 0, "indep_conf": 1, "recent": 2, "weighted_spherical": 3}
 
+# every symbol include/m3s_retrieval.h declares
+RETRIEVAL_EXPORTS = (
+    "m3s_asmk_store_size", "m3s_asmk_workspace_size", "m3s_asmk_store_layout", "m3s_asmk_workspace_layout",
+    "m3s_asmk_reset", "m3s_asmk_aggregate", "m3s_asmk_search", "m3s_asmk_append",
+)
+ASMK_MAX_PAIRS, ASMK_MAX_K = 4096, 64
+ASMK_INFO_BAD_WORD, ASMK_INFO_FULL = 1, 2
+ASMK_STORE_SECTIONS = ("header", "img_ptr", "word", "codes", "total")
+ASMK_WS_SECTIONS = ("counts", "slot", "words", "start", "members", "codes", "scores", "out", "total")
+
+
+class AsmkOut(ctypes.Structure):
+    """Mirror of ``m3s_asmk_out`` (include/m3s_retrieval.h)."""
+
+    _fields_ = [
+        ("count", ctypes.c_int32), ("n_images", ctypes.c_int32), ("info", ctypes.c_int32),
+        ("n_query_words", ctypes.c_int32), ("idx", ctypes.c_int32 * ASMK_MAX_K),
+        ("score", ctypes.c_double * ASMK_MAX_K),
+    ]
+
+
+class AsmkDb(ctypes.Structure):
+    """Mirror of ``m3s_asmk_db`` (include/m3s_retrieval.h)."""
+
+    _fields_ = [
+        ("store", _VP), ("store_bytes", ctypes.c_size_t), ("workspace", _VP), ("workspace_bytes", ctypes.c_size_t),
+        ("cap_images", ctypes.c_int64), ("cap_entries", ctypes.c_int64), ("Kc", ctypes.c_int64),
+        ("D", ctypes.c_int64),
+    ]
+
+
+class AsmkAggregateArgs(ctypes.Structure):
+    """Mirror of ``m3s_asmk_aggregate_args`` (include/m3s_retrieval.h)."""
+
+    _fields_ = [
+        ("db", AsmkDb), ("des", _VP), ("centroids", _VP), ("assign", _VP),
+        ("n", ctypes.c_int64), ("ma", ctypes.c_int64), ("query_ma", ctypes.c_int), ("build_ma", ctypes.c_int),
+    ]
+
+
+class AsmkSearchArgs(ctypes.Structure):
+    """Mirror of ``m3s_asmk_search_args`` (include/m3s_retrieval.h)."""
+
+    _fields_ = [
+        ("db", AsmkDb), ("n_images", ctypes.c_int64), ("k", ctypes.c_int), ("alpha", ctypes.c_float),
+        ("similarity_threshold", ctypes.c_float), ("min_thresh", ctypes.c_double),
+    ]
+
 
 def _load(path=LIB_PATH):
     if not os.path.exists(path):
@@ -234,6 +287,15 @@ def _load(path=LIB_PATH):
     lib.m3s_debug_call_times.argtypes = [_VP, _VP, ctypes.c_int]
     lib.m3s_gn_layout_debug.restype = ctypes.c_size_t
     lib.m3s_gn_layout_debug.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _VP]
+    for f in RETRIEVAL_EXPORTS:  # include/m3s_retrieval.h
+        fn = getattr(lib, f)
+        if f.endswith("_size") or f.endswith("_layout"):
+            fn.restype = ctypes.c_size_t
+            fn.argtypes = [ctypes.c_int64] * 3 + ([P(ctypes.c_size_t)] if f.endswith("_layout") else [])
+        else:
+            fn.restype = ctypes.c_int
+            fn.argtypes = [P({"m3s_asmk_aggregate": AsmkAggregateArgs,
+                              "m3s_asmk_search": AsmkSearchArgs}.get(f, AsmkDb)), _VP]
     return lib
 
 
@@ -723,6 +785,155 @@ def prep_rays(X11, X21):
     a.X11, a.X21, a.B, a.H, a.W, a.rays_img, a.pts_norm = _p(X11), _p(X21), B, H, W, _p(rays), _p(pts)
     _raise(_lib.m3s_prep_rays(ctypes.byref(a), _stream(dev)), "m3s_prep_rays")
     return rays, pts
+
+
+# ---------------------------------------------------------- retrieval ---
+def asmk_store_layout(cap_images, cap_entries, D):
+    """Byte offsets of the store's sections (ASMK_STORE_SECTIONS)."""
+    offs = (ctypes.c_size_t * len(ASMK_STORE_SECTIONS))()
+    _lib.m3s_asmk_store_layout(int(cap_images), int(cap_entries), int(D), offs)
+    return dict(zip(ASMK_STORE_SECTIONS, list(offs)))
+
+
+def asmk_workspace_layout(Kc, D, cap_images):
+    """Byte offsets of the workspace's sections (ASMK_WS_SECTIONS)."""
+    offs = (ctypes.c_size_t * len(ASMK_WS_SECTIONS))()
+    _lib.m3s_asmk_workspace_layout(int(Kc), int(D), int(cap_images), offs)
+    return dict(zip(ASMK_WS_SECTIONS, list(offs)))
+
+
+def asmk_store_size(cap_images, cap_entries, D):
+    return int(_lib.m3s_asmk_store_size(int(cap_images), int(cap_entries), int(D)))
+
+
+def asmk_workspace_size(Kc, D, cap_images):
+    return int(_lib.m3s_asmk_workspace_size(int(Kc), int(D), int(cap_images)))
+
+
+class AsmkHandle:
+    """One database for the m3s_asmk_* entry points: the store and workspace
+    tensors (uint8, on a ROCm device), the geometry and the filled
+    ``m3s_asmk_db``. ``section(name)`` / ``ws_section(name)`` are typed views of
+    the documented sections, for the caller's one read and for tests."""
+
+    def __init__(self, store, workspace, cap_images, cap_entries, Kc, D):
+        _check(store, "store", torch.uint8)
+        _check(workspace, "workspace", torch.uint8)
+        if store.device != workspace.device:
+            raise RuntimeError("asmk: store and workspace must be on one device")
+        self.cap_images, self.cap_entries, self.Kc, self.D = int(cap_images), int(cap_entries), int(Kc), int(D)
+        if min(self.cap_images, self.cap_entries, self.Kc, self.D) < 1:
+            raise RuntimeError("asmk: cap_images, cap_entries, Kc and D must be >= 1")
+        self.D32 = (self.D + 31) // 32
+        self.store_off = asmk_store_layout(self.cap_images, self.cap_entries, self.D)
+        self.ws_off = asmk_workspace_layout(self.Kc, self.D, self.cap_images)
+        if store.numel() < self.store_off["total"] or workspace.numel() < self.ws_off["total"]:
+            raise RuntimeError("asmk: store or workspace smaller than its size function says")
+        if store.data_ptr() % 16 or workspace.data_ptr() % 16:
+            raise RuntimeError("asmk: store and workspace must be 16-byte aligned")
+        self.store, self.workspace, self.device = store, workspace, store.device
+        d = AsmkDb()
+        d.store, d.store_bytes = _p(store), store.numel()
+        d.workspace, d.workspace_bytes = _p(workspace), workspace.numel()
+        d.cap_images, d.cap_entries, d.Kc, d.D = self.cap_images, self.cap_entries, self.Kc, self.D
+        self.db = d
+
+    @staticmethod
+    def _view(buf, off, count, dtype):
+        nbytes = count * torch.empty(0, dtype=dtype).element_size()
+        return buf[off:off + nbytes].view(dtype)
+
+    def section(self, name):
+        o = self.store_off[name]
+        if name == "header":
+            return self._view(self.store, o, 16, torch.int32)
+        if name == "img_ptr":
+            return self._view(self.store, o, self.cap_images + 1, torch.int32)
+        if name == "word":
+            return self._view(self.store, o, self.cap_entries, torch.int32)
+        if name == "codes":  # uint32 bit patterns as int32
+            return self._view(self.store, o, self.cap_entries * self.D32, torch.int32).view(-1, self.D32)
+        raise KeyError(name)
+
+    def ws_section(self, name):
+        o = self.ws_off[name]
+        if name == "counts":
+            return self._view(self.workspace, o, 16, torch.int32)
+        if name == "slot":
+            return self._view(self.workspace, o, self.Kc, torch.int32)
+        if name in ("words", "members"):
+            return self._view(self.workspace, o, 2 * ASMK_MAX_PAIRS, torch.int32).view(2, -1)
+        if name == "start":
+            return self._view(self.workspace, o, 2 * (ASMK_MAX_PAIRS + 16), torch.int32).view(2, -1)
+        if name == "codes":
+            return self._view(self.workspace, o, 2 * ASMK_MAX_PAIRS * self.D32, torch.int32).view(2, -1, self.D32)
+        if name == "scores":
+            return self._view(self.workspace, o, self.cap_images, torch.float64)
+        if name == "out":
+            return self.workspace[o:o + ctypes.sizeof(AsmkOut)]
+        raise KeyError(name)
+
+
+def asmk_reset(h: AsmkHandle):
+    """Empty the store and clear the word table (m3s_asmk_reset)."""
+    _raise(_lib.m3s_asmk_reset(ctypes.byref(h.db), _stream(h.device)), "m3s_asmk_reset")
+
+
+def asmk_aggregate(h: AsmkHandle, des, centroids, assign, query_ma, build_ma):
+    """m3s_asmk_aggregate: des [n, D] f32, centroids [Kc, D] f32, assign [n, ma]
+    int64 -> the query rows (first query_ma columns) and the build rows (first
+    build_ma columns) of the workspace. With query_ma > 0 an asmk_search must
+    follow before the next aggregate (it clears the word table)."""
+    _check(des, "des", torch.float32)
+    _check(centroids, "centroids", torch.float32)
+    _check(assign, "assign", torch.int64)
+    if des.dim() != 2 or des.shape[1] != h.D:
+        raise RuntimeError(f"asmk_aggregate: des must be [n, {h.D}]")
+    if tuple(centroids.shape) != (h.Kc, h.D):
+        raise RuntimeError(f"asmk_aggregate: centroids must be [{h.Kc}, {h.D}]")
+    n = int(des.shape[0])
+    if assign.dim() != 2 or assign.shape[0] != n:
+        raise RuntimeError("asmk_aggregate: assign must be [n, ma]")
+    ma, query_ma, build_ma = int(assign.shape[1]), int(query_ma), int(build_ma)
+    if not (0 <= query_ma <= ma and 0 <= build_ma <= ma and query_ma + build_ma > 0 and n >= 1):
+        raise RuntimeError("asmk_aggregate: need n >= 1 and 0 <= query_ma, build_ma <= ma, not both 0")
+    if n * max(query_ma, build_ma) > ASMK_MAX_PAIRS:
+        raise RuntimeError(f"asmk_aggregate: n * multiple_assignment exceeds {ASMK_MAX_PAIRS}")
+    for name, t in (("des", des), ("centroids", centroids), ("assign", assign)):
+        if t.device != h.device:
+            raise RuntimeError(f"asmk_aggregate: {name} is on {t.device}, the database on {h.device}")
+    a = AsmkAggregateArgs()
+    a.db = h.db
+    a.des, a.centroids, a.assign = _p(des), _p(centroids), _p(assign)
+    a.n, a.ma, a.query_ma, a.build_ma = n, ma, query_ma, build_ma
+    _raise(_lib.m3s_asmk_aggregate(ctypes.byref(a), _stream(h.device)), "m3s_asmk_aggregate")
+
+
+def asmk_search(h: AsmkHandle, n_images, k, alpha=3.0, similarity_threshold=0.0, min_thresh=0.0):
+    """m3s_asmk_search: scores of the query rows against the first n_images
+    stored images -> h.ws_section("scores")[:n_images], selection ->
+    h.ws_section("out") (an AsmkOut). No host synchronisation."""
+    n_images, k = int(n_images), int(k)
+    if not 1 <= n_images <= h.cap_images:
+        raise RuntimeError(f"asmk_search: n_images must be in [1, {h.cap_images}]")
+    if not 1 <= k <= ASMK_MAX_K:
+        raise RuntimeError(f"asmk_search: k must be in [1, {ASMK_MAX_K}]")
+    a = AsmkSearchArgs()
+    a.db = h.db
+    a.n_images, a.k = n_images, k
+    a.alpha, a.similarity_threshold, a.min_thresh = float(alpha), float(similarity_threshold), float(min_thresh)
+    _raise(_lib.m3s_asmk_search(ctypes.byref(a), _stream(h.device)), "m3s_asmk_search")
+
+
+def asmk_append(h: AsmkHandle):
+    """m3s_asmk_append: the build rows become the next stored image; at
+    capacity nothing is written but ASMK_INFO_FULL in the store header."""
+    _raise(_lib.m3s_asmk_append(ctypes.byref(h.db), _stream(h.device)), "m3s_asmk_append")
+
+
+def asmk_read_out(h: AsmkHandle) -> AsmkOut:
+    """The one device-to-host copy of a search: its ``m3s_asmk_out``."""
+    return AsmkOut.from_buffer_copy(h.ws_section("out").cpu().numpy().tobytes())
 
 
 # ------------------------------------------------------------ tracker ---
