@@ -13,6 +13,10 @@
  *               and the top-k of retrieval_database.py:59-67
  *   append      IVF.add (inverted_file.py:56-84) with use_idf=False
  *
+ * and that quantize itself (quantize_custom, retrieval_database.py:96-105), so
+ * that a C caller can run a whole retrieval: norms once, then per frame
+ * quantize -> aggregate -> search -> append.
+ *
  * Plain C: device pointers, sizes, the caller's hipStream_t as `void *`, an int
  * status (M3S_OK / M3S_EINVAL / M3S_ELAUNCH of m3s_gn.h). No allocation and no
  * host synchronisation in any entry point; the caller reads the `out` section
@@ -139,6 +143,48 @@ int m3s_asmk_search(const m3s_asmk_search_args *a, void *stream);
 /* Append the build set as the next image. One launch. When either capacity
  * would be exceeded nothing is written but M3S_ASMK_INFO_FULL. */
 int m3s_asmk_append(const m3s_asmk_db *db, void *stream);
+
+/*
+ * The quantize (quantize_custom, retrieval_database.py:96-105): the `ma`
+ * nearest centroids of every feature, nearest first, into the `assign` that
+ * m3s_asmk_aggregate takes. Ranked by |c|^2 - 2 q.c in exact fp32 (the
+ * f32-input MFMA; |q|^2 is the same for every centroid of a feature), in the
+ * order (value ascending, word ascending): exactly equal values come out
+ * lower word first, and a second run is bitwise identical. No [n, Kc] matrix
+ * is ever stored: one launch keeps the smallest pairs of every (feature, tile
+ * of 128 centroids) in registers and writes `ma` of them per tile to the
+ * workspace, a second launch merges the tiles of each feature. The workspace
+ * is scratch of its own (not the database's); nothing in it outlives a call.
+ *
+ * M3S_EINVAL, before any launch: a null pointer (`dist` may be null), n < 1,
+ * n * ma > M3S_ASMK_MAX_PAIRS, ma < 1, ma > M3S_ASMK_QUANTIZE_MAX_MA, ma > Kc,
+ * Kc >= 2^20, D < 1, a workspace smaller than its size function says or not
+ * 8-byte aligned. Any other n, Kc and D work.
+ */
+#define M3S_ASMK_QUANTIZE_MAX_MA 8
+
+typedef struct m3s_asmk_quantize_args {
+  const float *des;       /* [n, D] local descriptors                          */
+  const float *centroids; /* [Kc, D] codebook                                  */
+  const float *norms;     /* [Kc] |c|^2 (m3s_asmk_centroid_norms)              */
+  int64_t n, Kc, D;
+  int ma;           /* 1 .. min(M3S_ASMK_QUANTIZE_MAX_MA, Kc)                  */
+  int64_t *assign;  /* out [n, ma]: nearest words, nearest first               */
+  float *dist;      /* out [n, ma] or null: the ranked values |c|^2 - 2 q.c    */
+  void *workspace;  /* >= m3s_asmk_quantize_workspace_size(n, Kc, ma) bytes    */
+  size_t workspace_bytes;
+} m3s_asmk_quantize_args;
+
+/* Bytes of scratch for the partial candidate lists of n <= n_max features. */
+size_t m3s_asmk_quantize_workspace_size(int64_t n_max, int64_t Kc, int ma);
+
+/* norms[c] = |centroids[c]|^2, summed in fp64 and rounded once to fp32. One
+ * launch, once per database. M3S_EINVAL: a null pointer, Kc < 1, Kc >= 2^20,
+ * D < 1. */
+int m3s_asmk_centroid_norms(const float *centroids, int64_t Kc, int64_t D, float *norms, void *stream);
+
+/* Two launches on `stream`. */
+int m3s_asmk_quantize(const m3s_asmk_quantize_args *a, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 // m3s_retrieval.hip — MI355X (gfx950) ASMK retrieval kernels
 // (include/m3s_retrieval.h): what RetrievalDatabase.update runs on the host in
 // the reference (numpy loops over visual words, a Cython Hamming kernel, per-word
-// posting lists) as six launches on the caller's stream.
+// posting lists) as six launches on the caller's stream, and its torch quantize
+// as two more (the quantize section below).
 //
 //   aggregate  sort_pairs_kernel   one workgroup per set: bitonic sort of the
 //                                  (word, feature) keys in LDS, unique words,
@@ -12,6 +13,8 @@
 //              select_kernel       scale, top-k, threshold, clear the table
 //   append     append_kernel       one workgroup: copy, then bump the counters
 //   reset      reset_kernel
+//   quantize   quantize_tile_kernel, quantize_merge_kernel (centroid_norms_kernel
+//              once per database)
 //
 // Every sum has a fixed order: the residual sums add features in ascending
 // order one after the other (numpy's .sum(0) over rows), the scores add in
@@ -389,6 +392,271 @@ __global__ void __launch_bounds__(kAppendThreads) append_kernel(Db db) {
   }
 }
 
+// ------------------------------------------------------------- quantize --
+// The nearest `ma` centroids of every feature by |c|^2 - 2 q.c (|q|^2 is the
+// same for every centroid of a feature), without a distance matrix.
+//
+//   quantize_tile_kernel   one workgroup per (128 centroids, 128 features):
+//                          the f32 MFMA product over D through LDS, then per
+//                          feature the ma smallest (value, word) pairs
+//                          of the tile -> workspace [n, tiles, ma]
+//   quantize_merge_kernel  one wave per feature: the smallest `ma` pairs over
+//                          its tiles -> assign (and dist)
+//
+// The order is (value ascending, word ascending) everywhere, a strict total
+// order on the pairs of one feature, so no merge order can change the result.
+
+constexpr int kQTile = 128;       // centroids and features per workgroup
+constexpr int kQK = 32;           // k per LDS tile
+constexpr int kQChain = 128;      // components per fmaf chain
+constexpr int kQStride = kQK + 4; // row stride in floats: ds_read_b128 of 16 rows hits 16 distinct 16-B slots
+constexpr int kQThreads = 256;
+constexpr int kQMaxMa = M3S_ASMK_QUANTIZE_MAX_MA;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+inline int64_t quantize_tiles(int64_t Kc) { return (Kc + kQTile - 1) / kQTile; }
+
+size_t quantize_workspace(int64_t n_max, int64_t Kc, int ma) {
+  if (n_max < 1 || Kc < 1 || ma < 1) return 0;
+  return align_up((size_t)n_max * (size_t)quantize_tiles(Kc) * (size_t)ma * sizeof(uint64_t));
+}
+
+// A (value, word) pair as one 64-bit key whose unsigned order is (value
+// ascending, word ascending): the value's bits made monotone (sign flipped for
+// v >= 0, all bits for v < 0; -0 is +0 first, so that equal values have equal
+// bits) above the word.
+__device__ inline uint64_t pair_key(float v, uint32_t w) {
+  const uint32_t b = __float_as_uint(v + 0.f);
+  return ((uint64_t)(b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u)) << 32) | w;
+}
+__device__ inline float key_value(uint64_t k) {
+  const uint32_t u = (uint32_t)(k >> 32);
+  return __uint_as_float(u ^ ((u & 0x80000000u) ? 0x80000000u : 0xffffffffu));
+}
+constexpr uint64_t kNoPair = ~0ull;  // an empty slot: after every pair of a word < 2^20
+
+// The M smallest keys seen, ascending, in registers (every loop is unrolled).
+template <int M>
+struct TopList {
+  uint64_t key[M];
+  __device__ inline void clear() {
+#pragma unroll
+    for (int j = 0; j < M; j++) key[j] = kNoPair;
+  }
+  __device__ inline void insert(uint64_t k) {  // one bubble pass: the largest of the M + 1 falls out
+#pragma unroll
+    for (int j = 0; j < M; j++) {
+      const bool lt = k < key[j];
+      const uint64_t lo = lt ? k : key[j];
+      k = lt ? key[j] : k;
+      key[j] = lo;
+    }
+  }
+  // the list of the lane `mask` away joins this one (both lanes end up equal)
+  __device__ inline void merge_xor(int mask) {
+    uint64_t other[M];
+#pragma unroll
+    for (int j = 0; j < M; j++) other[j] = __shfl_xor((unsigned long long)key[j], mask, 64);
+#pragma unroll
+    for (int j = 0; j < M; j++) insert(other[j]);
+  }
+};
+
+struct QuantArgs {
+  const float *des;
+  const float *centroids;
+  const float *norms;
+  int64_t *assign;
+  float *dist;
+  uint64_t *cand;  // [n, tiles, ma]: pair keys
+  int64_t D;
+  int32_t n, Kc, tiles, vec;
+};
+
+// One wave per centroid: lane l adds the squares of components l, l + 64, ...
+// in fp64, a fixed tree joins the lanes, one rounding to fp32.
+__global__ void __launch_bounds__(256) centroid_norms_kernel(const float *centroids, int32_t Kc, int64_t D, float *norms) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= Kc) return;
+  const float *row = centroids + (int64_t)c * D;
+  double acc = 0.0;
+  for (int64_t k = lane; k < D; k += 64) acc += (double)row[k] * (double)row[k];
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if (lane == 0) norms[c] = (float)acc;
+}
+
+// Rows row0 + r (r = tid / 8 + 32 i) of a [rows, D] matrix, components
+// k0 + 4 (tid % 8) .. + 3, zero outside the matrix.
+__device__ inline void quantize_fetch(const float *base, int64_t rows, int64_t D, int64_t row0, int64_t k0, bool vec,
+                                      int tid, float4 (&reg)[4]) {
+  const int64_t k = k0 + 4 * (tid & 7);
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int64_t r = row0 + (tid >> 3) + 32 * i;
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r < rows) {
+      const float *p = base + r * D + k;
+      if (vec) {
+        if (k < D) x = *reinterpret_cast<const float4 *>(p);  // D % 4 == 0: all four or none
+      } else {
+        if (k < D) x.x = p[0];
+        if (k + 1 < D) x.y = p[1];
+        if (k + 2 < D) x.z = p[2];
+        if (k + 3 < D) x.w = p[3];
+      }
+    }
+    reg[i] = x;
+  }
+}
+
+__device__ inline void quantize_stage(float *tile, int tid, const float4 (&reg)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    *reinterpret_cast<float4 *>(tile + ((tid >> 3) + 32 * i) * kQStride + 4 * (tid & 7)) = reg[i];
+}
+
+// Wave w of four takes centroids 64 (w / 2) .. + 63 and features 64 (w % 2)
+// .. + 63 of the workgroup's tile as 2 x 2 MFMA tiles: centroids on the row
+// index (A), features on the column index (B, the lane), so the 16
+// accumulators of a lane are 16 centroids of one feature. Lane half h takes
+// components 16 h .. 16 h + 15 of a 32-component LDS tile in its 16 k-steps
+// (A and B alike, so every product pairs the same component).
+template <int MA>
+__global__ void __launch_bounds__(kQThreads, 2) quantize_tile_kernel(QuantArgs A) {
+  __shared__ __attribute__((aligned(16))) float As[kQTile * kQStride];
+  __shared__ __attribute__((aligned(16))) float Bs[kQTile * kQStride];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
+  const int64_t c0 = (int64_t)blockIdx.x * kQTile, f0 = (int64_t)blockIdx.y * kQTile;
+  const bool vec = A.vec != 0;
+
+  // acc: the fmaf chain of the current kQChain components; dot: the sum of
+  // the finished chains. One chain over all of D loses too much when every
+  // product has the same sign (a feature next to its own centroid): at
+  // D = 1024 its error reaches 1e-6 of |c|^2 + 2 sum |q_k c_k|, eight chains
+  // of 128 stay below 2e-7.
+  f32x16 acc[2][2], dot[2][2];
+#pragma unroll
+  for (int m = 0; m < 2; m++)
+#pragma unroll
+    for (int nn = 0; nn < 2; nn++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[m][nn][r] = 0.f, dot[m][nn][r] = 0.f;
+
+  float4 ra[4], rb[4];
+  quantize_fetch(A.centroids, A.Kc, A.D, c0, 0, vec, tid, ra);
+  quantize_fetch(A.des, A.n, A.D, f0, 0, vec, tid, rb);
+  for (int64_t k0 = 0; k0 < A.D; k0 += kQK) {
+    quantize_stage(As, tid, ra);
+    quantize_stage(Bs, tid, rb);
+    __syncthreads();
+    if (k0 + kQK < A.D) {  // the next tile's loads fly under this tile's products
+      quantize_fetch(A.centroids, A.Kc, A.D, c0, k0 + kQK, vec, tid, ra);
+      quantize_fetch(A.des, A.n, A.D, f0, k0 + kQK, vec, tid, rb);
+    }
+    const float *ap = As + (wm * 64 + li) * kQStride + 16 * lh;
+    const float *bp = Bs + (wn * 64 + li) * kQStride + 16 * lh;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const float4 a0 = *reinterpret_cast<const float4 *>(ap + 4 * q);
+      const float4 a1 = *reinterpret_cast<const float4 *>(ap + 32 * kQStride + 4 * q);
+      const float4 b0 = *reinterpret_cast<const float4 *>(bp + 4 * q);
+      const float4 b1 = *reinterpret_cast<const float4 *>(bp + 32 * kQStride + 4 * q);
+      const float av[2][4] = {{a0.x, a0.y, a0.z, a0.w}, {a1.x, a1.y, a1.z, a1.w}};
+      const float bv[2][4] = {{b0.x, b0.y, b0.z, b0.w}, {b1.x, b1.y, b1.z, b1.w}};
+#pragma unroll
+      for (int s = 0; s < 4; s++)
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+          for (int nn = 0; nn < 2; nn++)
+            acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m][s], bv[nn][s], acc[m][nn], 0, 0, 0);
+    }
+    if ((k0 + kQK) % kQChain == 0 || k0 + kQK >= A.D) {
+#pragma unroll
+      for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int nn = 0; nn < 2; nn++)
+#pragma unroll
+          for (int r = 0; r < 16; r++) dot[m][nn][r] += acc[m][nn][r], acc[m][nn][r] = 0.f;
+    }
+    __syncthreads();
+  }
+
+  // this lane's 32 centroids of each of its two features, then the other lane
+  // half's (the centroids 4 rows on)
+  TopList<MA> top[2];
+#pragma unroll
+  for (int nn = 0; nn < 2; nn++) {
+    top[nn].clear();
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int64_t c = c0 + wm * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        // a row past Kc never takes a slot
+        top[nn].insert(c < A.Kc ? pair_key(fmaf(-2.f, dot[m][nn][r], A.norms[c]), (uint32_t)c) : kNoPair);
+      }
+    top[nn].merge_xor(32);
+  }
+  // the upper centroid half's lists go through LDS (the k loop's last barrier
+  // has passed: the tiles are free) to the lower half's waves
+  uint64_t *xch = reinterpret_cast<uint64_t *>(As);  // [MA][2][2 feature halves * 32 lanes]
+  if (wm == 1 && lh == 0) {
+#pragma unroll
+    for (int nn = 0; nn < 2; nn++)
+#pragma unroll
+      for (int j = 0; j < MA; j++) xch[(j * 2 + nn) * 64 + wn * 32 + li] = top[nn].key[j];
+  }
+  __syncthreads();
+  if (wm == 0 && lh == 0) {
+#pragma unroll
+    for (int nn = 0; nn < 2; nn++) {
+#pragma unroll
+      for (int j = 0; j < MA; j++) top[nn].insert(xch[(j * 2 + nn) * 64 + wn * 32 + li]);
+      const int64_t f = f0 + wn * 64 + nn * 32 + li;
+      if (f < A.n) {  // feature tail: computed and dropped
+        uint64_t *out = A.cand + (f * A.tiles + blockIdx.x) * MA;
+#pragma unroll
+        for (int j = 0; j < MA; j++) out[j] = top[nn].key[j];
+      }
+    }
+  }
+}
+
+// One wave per feature: lane l takes candidates l, l + 64, ... of the
+// feature's tiles * ma, a butterfly joins the lanes, lane j writes rank j.
+template <int MA>
+__global__ void __launch_bounds__(256) quantize_merge_kernel(QuantArgs A) {
+  const int f = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (f >= A.n) return;
+  const int64_t count = (int64_t)A.tiles * MA;
+  const uint64_t *cand = A.cand + (int64_t)f * count;
+  TopList<MA> top;
+  top.clear();
+  for (int64_t e = lane; e < count; e += 64) top.insert(cand[e]);
+  for (int off = 32; off > 0; off >>= 1) top.merge_xor(off);
+#pragma unroll
+  for (int j = 0; j < MA; j++)
+    if (lane == j) {
+      // ma <= Kc: an empty slot can only come out of non-finite input; it is
+      // -1, which m3s_asmk_aggregate skips as a bad word
+      const uint32_t w = (uint32_t)top.key[j];
+      A.assign[(int64_t)f * MA + j] = w < (uint32_t)A.Kc ? (int64_t)w : -1;
+      if (A.dist) A.dist[(int64_t)f * MA + j] = w < (uint32_t)A.Kc ? key_value(top.key[j]) : INFINITY;
+    }
+}
+
+template <int MA>
+int launch_quantize(const QuantArgs &A, hipStream_t st) {
+  const dim3 grid((unsigned)A.tiles, (unsigned)((A.n + kQTile - 1) / kQTile));
+  quantize_tile_kernel<MA><<<grid, kQThreads, 0, st>>>(A);
+  if (launch_status() != M3S_OK) return M3S_ELAUNCH;
+  quantize_merge_kernel<MA><<<(unsigned)((A.n + 3) / 4), 256, 0, st>>>(A);
+  return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -455,6 +723,38 @@ int m3s_asmk_append(const m3s_asmk_db *d, void *stream) {
   if (!make_db(d, &db)) return M3S_EINVAL;
   append_kernel<<<1, kAppendThreads, 0, static_cast<hipStream_t>(stream)>>>(db);
   return launch_status();
+}
+
+size_t m3s_asmk_quantize_workspace_size(int64_t n_max, int64_t Kc, int ma) { return quantize_workspace(n_max, Kc, ma); }
+
+int m3s_asmk_centroid_norms(const float *centroids, int64_t Kc, int64_t D, float *norms, void *stream) {
+  if (!centroids || !norms || Kc < 1 || Kc > kMaxWords || D < 1) return M3S_EINVAL;
+  centroid_norms_kernel<<<(unsigned)((Kc + 3) / 4), 256, 0, static_cast<hipStream_t>(stream)>>>(centroids, (int32_t)Kc, D,
+                                                                                                 norms);
+  return launch_status();
+}
+
+int m3s_asmk_quantize(const m3s_asmk_quantize_args *a, void *stream) {
+  if (!a || !a->des || !a->centroids || !a->norms || !a->assign || !a->workspace) return M3S_EINVAL;
+  if (a->n < 1 || a->ma < 1 || a->ma > kQMaxMa || a->ma > a->Kc || a->n * a->ma > kMaxPairs) return M3S_EINVAL;
+  if (a->Kc > kMaxWords || a->D < 1) return M3S_EINVAL;
+  if (a->workspace_bytes < quantize_workspace(a->n, a->Kc, a->ma) || ((uintptr_t)a->workspace & 7)) return M3S_EINVAL;
+  QuantArgs A;
+  A.des = a->des, A.centroids = a->centroids, A.norms = a->norms, A.assign = a->assign, A.dist = a->dist;
+  A.cand = static_cast<uint64_t *>(a->workspace);
+  A.D = a->D, A.n = (int32_t)a->n, A.Kc = (int32_t)a->Kc, A.tiles = (int32_t)quantize_tiles(a->Kc);
+  A.vec = (a->D % 4 == 0 && (((uintptr_t)a->des | (uintptr_t)a->centroids) & 15) == 0) ? 1 : 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (a->ma) {  // the list length is a compile-time constant: the lists live in registers
+    case 1: return launch_quantize<1>(A, st);
+    case 2: return launch_quantize<2>(A, st);
+    case 3: return launch_quantize<3>(A, st);
+    case 4: return launch_quantize<4>(A, st);
+    case 5: return launch_quantize<5>(A, st);
+    case 6: return launch_quantize<6>(A, st);
+    case 7: return launch_quantize<7>(A, st);
+    default: return launch_quantize<8>(A, st);
+  }
 }
 
 }  // extern "C"

@@ -4,12 +4,14 @@ faiss, the per-keyframe copy of the features to the host and the Python loops
 over visual words.
 
 The quantize (``quantize_custom``, :96-105) is torch on the device, as in the
-reference. Everything after it -- residual aggregation, binarisation and
-packing, the inverted file, the Hamming similarity, the score accumulation and
-the top-k -- is the HIP code behind ``mast3r_slam_backends.asmk_*``
-(include/m3s_retrieval.h). The parameters are the ones MASt3R fixes
-(mast3r/retrieval/processor.py:91-96): binary kernel, no idf, multiple
-assignment 1 for the build and 5 for the query, alpha 3, similarity threshold 0.
+reference, or with ``quantizer="device"`` the fused distance and top-MA kernel
+``mast3r_slam_backends.asmk_quantize`` (no distance matrix). Everything after
+it -- residual aggregation, binarisation and packing, the inverted file, the
+Hamming similarity, the score accumulation and the top-k -- is the HIP code
+behind ``mast3r_slam_backends.asmk_*`` (include/m3s_retrieval.h). The
+parameters are the ones MASt3R fixes (mast3r/retrieval/processor.py:91-96):
+binary kernel, no idf, multiple assignment 1 for the build and 5 for the query,
+alpha 3, similarity threshold 0.
 
 The retrieval network and ``prep_features`` are not part of this class: ``feat``
 is what ``prep_features`` returns.
@@ -42,14 +44,18 @@ class RetrievalDatabase:
     is empty."""
 
     def __init__(self, centroids, capacity=512, max_features=300, query_ma=5, build_ma=1, alpha=3.0,
-                 similarity_threshold=0.0, *, use_idf=False, binary=True):
+                 similarity_threshold=0.0, *, use_idf=False, binary=True, quantizer="torch"):
         if use_idf:
             raise ValueError("RetrievalDatabase: use_idf=True is not supported (idf is 1 throughout)")
         if binary not in (True, "bin"):
             raise ValueError("RetrievalDatabase: only the binary ASMK kernel is supported")
+        if quantizer not in ("torch", "device"):
+            raise ValueError(f"RetrievalDatabase: quantizer must be 'torch' or 'device' (got {quantizer!r})")
         capacity, max_features, query_ma, build_ma = int(capacity), int(max_features), int(query_ma), int(build_ma)
         if capacity < 1 or max_features < 1 or build_ma < 1 or query_ma < build_ma:
             raise ValueError("RetrievalDatabase: need capacity, max_features >= 1 and 1 <= build_ma <= query_ma")
+        if quantizer == "device" and query_ma > be.ASMK_QUANTIZE_MAX_MA:
+            raise ValueError(f"RetrievalDatabase: quantizer='device' takes query_ma <= {be.ASMK_QUANTIZE_MAX_MA}")
         if max_features * query_ma > be.ASMK_MAX_PAIRS:
             raise ValueError(f"RetrievalDatabase: max_features * query_ma = {max_features * query_ma} exceeds "
                              f"{be.ASMK_MAX_PAIRS} (n * multiple_assignment of one aggregate)")
@@ -69,6 +75,14 @@ class RetrievalDatabase:
         ws = torch.empty(be.asmk_workspace_size(self.Kc, self.D, capacity), dtype=torch.uint8, device=self.device)
         self.handle = be.AsmkHandle(store, ws, capacity, cap_entries, self.Kc, self.D)
         be.asmk_reset(self.handle)
+        self.quantizer = quantizer
+        if quantizer == "device":  # everything m3s_asmk_quantize needs, once: no allocation per call
+            if query_ma > self.Kc:
+                raise ValueError(f"RetrievalDatabase: query_ma = {query_ma} exceeds the {self.Kc} centroids")
+            self.centroid_norms = be.asmk_centroid_norms(self.centroids)
+            self._quantize_ws = torch.empty(be.asmk_quantize_workspace_size(max_features, self.Kc, query_ma),
+                                            dtype=torch.uint8, device=self.device)
+            self._assign = torch.empty(max_features * query_ma, dtype=torch.int64, device=self.device)
         self.kf_counter = 0
         self.kf_ids = []
 
@@ -88,7 +102,16 @@ class RetrievalDatabase:
 
     def quantize(self, feat, multiple_assignment):
         """quantize_custom (:96-105): the ``multiple_assignment`` nearest
-        centroids of every feature, nearest first -> [n, ma] int64."""
+        centroids of every feature, nearest first -> [n, ma] int64. With
+        ``quantizer="device"`` it is m3s_asmk_quantize and the result is a view
+        of the database's own buffer, valid until the next quantize."""
+        if self.quantizer == "device":
+            n, ma = int(feat.shape[0]), int(multiple_assignment)
+            if not (1 <= n <= self.max_features and 1 <= ma <= self.query_ma):
+                raise RuntimeError(f"RetrievalDatabase: the device quantizer was sized for n <= {self.max_features} "
+                                   f"and multiple_assignment <= {self.query_ma}")
+            return be.asmk_quantize(feat, self.centroids, self.centroid_norms, ma, self._quantize_ws,
+                                    out=self._assign[:n * ma].view(n, ma))
         l2_dists = (
             torch.sum(feat**2, dim=1)[:, None]
             + self.centroids_sq[None, :]

@@ -30,6 +30,9 @@ GN entry points, the edge store and the trackers consume, in three launches.
 reference runs on the host after its torch quantize: aggregate (residual sums,
 binarise, pack), search (Hamming similarity, scores, top-k) and append, on an
 ``AsmkHandle``; ``mast3r_slam_amd.retrieval.RetrievalDatabase`` is built on them.
+``asmk_centroid_norms`` and ``asmk_quantize`` are that quantize itself as a
+fused distance and top-MA kernel (no distance matrix), for callers without torch
+and for ``RetrievalDatabase(quantizer="device")``.
 """
 from __future__ import annotations
 
@@ -182,8 +185,10 @@ FILTER_MODES = {"weighted_pointmap": 0, "indep_conf": 1, "recent": 2, "weighted_
 RETRIEVAL_EXPORTS = (
     "m3s_asmk_store_size", "m3s_asmk_workspace_size", "m3s_asmk_store_layout", "m3s_asmk_workspace_layout",
     "m3s_asmk_reset", "m3s_asmk_aggregate", "m3s_asmk_search", "m3s_asmk_append",
+    "m3s_asmk_quantize_workspace_size", "m3s_asmk_centroid_norms", "m3s_asmk_quantize",
 )
 ASMK_MAX_PAIRS, ASMK_MAX_K = 4096, 64
+ASMK_QUANTIZE_MAX_MA = 8
 ASMK_INFO_BAD_WORD, ASMK_INFO_FULL = 1, 2
 ASMK_STORE_SECTIONS = ("header", "img_ptr", "word", "codes", "total")
 ASMK_WS_SECTIONS = ("counts", "slot", "words", "start", "members", "codes", "scores", "out", "total")
@@ -224,6 +229,16 @@ class AsmkSearchArgs(ctypes.Structure):
     _fields_ = [
         ("db", AsmkDb), ("n_images", ctypes.c_int64), ("k", ctypes.c_int), ("alpha", ctypes.c_float),
         ("similarity_threshold", ctypes.c_float), ("min_thresh", ctypes.c_double),
+    ]
+
+
+class AsmkQuantizeArgs(ctypes.Structure):
+    """Mirror of ``m3s_asmk_quantize_args`` (include/m3s_retrieval.h)."""
+
+    _fields_ = [
+        ("des", _VP), ("centroids", _VP), ("norms", _VP),
+        ("n", ctypes.c_int64), ("Kc", ctypes.c_int64), ("D", ctypes.c_int64), ("ma", ctypes.c_int),
+        ("assign", _VP), ("dist", _VP), ("workspace", _VP), ("workspace_bytes", ctypes.c_size_t),
     ]
 
 
@@ -289,13 +304,20 @@ def _load(path=LIB_PATH):
     lib.m3s_gn_layout_debug.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _VP]
     for f in RETRIEVAL_EXPORTS:  # include/m3s_retrieval.h
         fn = getattr(lib, f)
-        if f.endswith("_size") or f.endswith("_layout"):
+        if f == "m3s_asmk_quantize_workspace_size":
+            fn.restype = ctypes.c_size_t
+            fn.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
+        elif f == "m3s_asmk_centroid_norms":
+            fn.restype = ctypes.c_int
+            fn.argtypes = [_VP, ctypes.c_int64, ctypes.c_int64, _VP, _VP]
+        elif f.endswith("_size") or f.endswith("_layout"):
             fn.restype = ctypes.c_size_t
             fn.argtypes = [ctypes.c_int64] * 3 + ([P(ctypes.c_size_t)] if f.endswith("_layout") else [])
         else:
             fn.restype = ctypes.c_int
             fn.argtypes = [P({"m3s_asmk_aggregate": AsmkAggregateArgs,
-                              "m3s_asmk_search": AsmkSearchArgs}.get(f, AsmkDb)), _VP]
+                              "m3s_asmk_search": AsmkSearchArgs,
+                              "m3s_asmk_quantize": AsmkQuantizeArgs}.get(f, AsmkDb)), _VP]
     return lib
 
 
@@ -934,6 +956,70 @@ def asmk_append(h: AsmkHandle):
 def asmk_read_out(h: AsmkHandle) -> AsmkOut:
     """The one device-to-host copy of a search: its ``m3s_asmk_out``."""
     return AsmkOut.from_buffer_copy(h.ws_section("out").cpu().numpy().tobytes())
+
+
+def asmk_quantize_workspace_size(n_max, Kc, ma):
+    """Bytes of scratch ``asmk_quantize`` needs for up to ``n_max`` features."""
+    return int(_lib.m3s_asmk_quantize_workspace_size(int(n_max), int(Kc), int(ma)))
+
+
+def asmk_centroid_norms(centroids):
+    """m3s_asmk_centroid_norms: centroids [Kc, D] f32 -> |c|^2 [Kc] f32, once
+    per codebook. One launch on the current stream."""
+    _check(centroids, "centroids", torch.float32)
+    if centroids.dim() != 2 or centroids.shape[0] < 1 or centroids.shape[1] < 1:
+        raise RuntimeError("asmk_centroid_norms: centroids must be [Kc, D]")
+    Kc, D = (int(x) for x in centroids.shape)
+    norms = torch.empty(Kc, dtype=torch.float32, device=centroids.device)
+    _raise(_lib.m3s_asmk_centroid_norms(_p(centroids), Kc, D, _p(norms), _stream(centroids.device)),
+           "m3s_asmk_centroid_norms")
+    return norms
+
+
+def asmk_quantize(feat, centroids, norms, ma, workspace, out=None, dist=None):
+    """m3s_asmk_quantize: feat [n, D] f32, centroids [Kc, D] f32, norms [Kc]
+    (asmk_centroid_norms) -> the ``ma`` nearest words of every feature, nearest
+    first, [n, ma] int64 (``out``, or a new tensor): the ``assign`` of
+    asmk_aggregate. ``workspace`` is a uint8 buffer of at least
+    asmk_quantize_workspace_size(n, Kc, ma) bytes; ``dist`` ([n, ma] f32,
+    optional) receives the ranked values |c|^2 - 2 q.c. Two launches on the
+    current stream, no allocation when ``out`` is given, no host
+    synchronisation."""
+    _check(feat, "feat", torch.float32)
+    _check(centroids, "centroids", torch.float32)
+    _check(norms, "norms", torch.float32)
+    _check(workspace, "workspace", torch.uint8)
+    if feat.dim() != 2 or centroids.dim() != 2 or feat.shape[1] != centroids.shape[1]:
+        raise RuntimeError("asmk_quantize: feat must be [n, D] and centroids [Kc, D]")
+    n, D = (int(x) for x in feat.shape)
+    Kc, ma = int(centroids.shape[0]), int(ma)
+    if tuple(norms.shape) != (Kc,):
+        raise RuntimeError(f"asmk_quantize: norms must be [{Kc}]")
+    if not 1 <= ma <= min(ASMK_QUANTIZE_MAX_MA, Kc):
+        raise RuntimeError(f"asmk_quantize: ma must be in [1, min({ASMK_QUANTIZE_MAX_MA}, Kc)]")
+    if n < 1 or n * ma > ASMK_MAX_PAIRS:
+        raise RuntimeError(f"asmk_quantize: need n >= 1 and n * ma <= {ASMK_MAX_PAIRS}")
+    if workspace.numel() < asmk_quantize_workspace_size(n, Kc, ma):
+        raise RuntimeError("asmk_quantize: workspace smaller than asmk_quantize_workspace_size(n, Kc, ma)")
+    if out is None:
+        out = torch.empty((n, ma), dtype=torch.int64, device=feat.device)
+    _check(out, "out", torch.int64)
+    if tuple(out.shape) != (n, ma):
+        raise RuntimeError(f"asmk_quantize: out must be [{n}, {ma}]")
+    if dist is not None:
+        _check(dist, "dist", torch.float32)
+        if tuple(dist.shape) != (n, ma):
+            raise RuntimeError(f"asmk_quantize: dist must be [{n}, {ma}]")
+    for name, t in (("centroids", centroids), ("norms", norms), ("workspace", workspace), ("out", out), ("dist", dist)):
+        if t is not None and t.device != feat.device:
+            raise RuntimeError(f"asmk_quantize: {name} is on {t.device}, feat on {feat.device}")
+    a = AsmkQuantizeArgs()
+    a.des, a.centroids, a.norms = _p(feat), _p(centroids), _p(norms)
+    a.n, a.Kc, a.D, a.ma = n, Kc, D, ma
+    a.assign, a.dist = _p(out), _p(dist)
+    a.workspace, a.workspace_bytes = _p(workspace), workspace.numel()
+    _raise(_lib.m3s_asmk_quantize(ctypes.byref(a), _stream(feat.device)), "m3s_asmk_quantize")
+    return out
 
 
 # ------------------------------------------------------------ tracker ---
