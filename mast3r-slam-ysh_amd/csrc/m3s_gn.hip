@@ -1,32 +1,59 @@
-// m3s_gn.hip — MI355X (gfx950) Gauss-Newton backend for MASt3R-SLAM.
+// m3s_gn.hip — MI355X (gfx950) Gauss-Newton backend and tracker for MASt3R-SLAM.
 //
-// One GN iteration of the backend (gauss_newton_{points,rays,calib}) is four
-// launches on the caller's stream, no host synchronisation:
+// One translation unit: the backend below, section by section, then the
+// tracker (gn/track.h) and the track_frame front end (gn/track_frame.h), then
+// the two debug kernels and the C exports. The gn/*.h files are parts of this
+// file, not stand-alone headers: each reopens the anonymous namespace and
+// relies on what stands before it. Every launch is on the caller's stream; a
+// call does not wait for the device except where noted. Sections are named by
+// their rule lines (`// ---- name --`).
 //
-//   linearize_kernel   grid = E_loc x chunks, 256 threads. Each block streams a
-//                      pixel chunk of one directed edge (idx/valid/Q/Xj/Cj
-//                      coalesced 16 B per lane, Xi/Ci gathered through
-//                      idx), builds the residual rows and accumulates the
-//                      28+7+1 local normal-equation sums in registers, then a
-//                      wave64 butterfly + LDS reduce -> one 36-float partial.
-//                      (replaces ray_align_kernel / calib_proj_kernel /
-//                      point_align_kernel, gn_kernels.cu:455-1543)
-//   edge_reduce_kernel fp64 sum of an edge's chunk partials in fixed order
-//                      (deterministic, no float atomics).
-//   assemble_kernel    one block per pose row: H_jj = M L M^T per touching
-//                      edge (M = Adj(T_i)^-T), +-H_jj into the dense fp64
-//                      system, g likewise. (replaces SparseBlock::update_lhs/
-//                      update_rhs, gn_kernels.cu:71-113, which ran on the CPU)
-//   chol_small_kernel  one 512-thread block: register-resident fp64 Cholesky
-//                      of the RHS-augmented system (forward solve for free),
-//                      blocked back-substitution, dx = -x, Sim3 retraction of
-//                      poses 1..N-1, ||dx|| < delta -> device stop flag.
-//                      (replaces Eigen SimplicialLLT on the host + the D2H/H2D
-//                      copies + pose_retr_kernel + .item() sync,
-//                      gn_kernels.cu:132-153, :1199-1222)
+// gauss_newton_{points,rays,calib} (gn_full, section host):
+//   prepare    gn_prologue_kernel (call prologue): ranks the edge ids, writes the
+//              linearize edge order, flags, info, dx; the ids go to pinned memory
+//              and the host builds (or fetches from the plan cache) the symbolic
+//              plan while the first linearize runs. Above 2048 edges: the host
+//              prepare (one stream sync, gn_prepare_impl).
+//   iteration  1 linearize launch; its last chunk of an edge finalizes the edge:
+//                first iteration   linearize_gather_kernel (pipelined gathering
+//                                  launch), or linearize_kernel (linearize)
+//                                  where the gathering kernel does not apply
+//                later iterations  linearize_packed_kernel (linearize)
+//              then the solve (gn_solve_impl), by the plan:
+//                factor fits the LDS (small graphs): sparse_llt_kernel<1> / <2>,
+//                  one workgroup: assembly, LLT, back-substitution, retraction,
+//                  stop flag (block-sparse LLT; assemble_slots_kernel first when
+//                  the staged edge blocks do not fit beside the factor)
+//                else, up to 512 columns (large graphs), over the chip:
+//                  assemble_slots_kernel (block-sparse LLT),
+//                  df_factor_kernel (wave-level dataflow factorisation),
+//                  tail_pair_kernel when the plan has a dense tail (under the
+//                  bare rule behind the dense tail sections, "Round 5"; from 32
+//                  tail columns its extra workgroups run the sparse back-
+//                  substitution, gcol_worker), else col_backsub_kernel (dataflow)
+//                else: sparse_llt_kernel<0>, in two phases around border_kernel
+//                  (border kernel) and tail_llt_kernel (dense tail on the f64
+//                  MFMA) with a dense tail
+//                no sparse plan that fits: edge_reduce_kernel (gathering launch),
+//                  assemble_kernel and the tiled dense Cholesky (assemble)
+//   The stepwise API (m3s_gn_prepare / _linearize / _solve, sharded ranks) runs
+//   the same launches, with finalize_edges_kernel ahead of a sparse solve.
+// track_{rays,calib}_sim3 (track_impl, gn/track.h): track_init_kernel, then
+//   track_persistent_kernel (every iteration in one launch), or per iteration
+//   one linearize_kernel<MODE, TRACK> whose last chunk runs track_solve_block.
+//   calib reads K back once (a stream sync).
+// track_frame (track_frame_impl, gn/track_frame.h): track_prep_clear_kernel,
+//   track_prep_kernel, track_prep_count_kernel, then the tracker's launches.
+// The test build (-DM3S_TEST_PATHS) adds the A/B reference paths behind the
+// test-only knobs (host): col_factor_kernel (column tasks), chol_small_kernel
+// (small dense Cholesky), tail_cyc_kernel, the VGPR-staged gathering kernel.
 //
-// The tracker entry points reuse linearize_kernel (no gather, frame-local
-// Jacobian) plus a one-block 7x7 solve/convergence kernel.
+// Order rule: device functions and kernels keep their relative order, and so
+// does the order in which host code first names each kernel template (that
+// decides where its instantiation lands). The code object holds real calls to
+// non-inlined device functions, so a reordering changes pc-relative literals
+// and the device code can no longer be compared instruction for instruction
+// with the build before (tools/code_identity.py). Host code may move otherwise.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -4789,6 +4816,31 @@ inline int prologue_p2(int64_t E) {
   return p;
 }
 
+// ------------------------------------------------------- border kernel --
+// Dense-tail border updates spread over the chip (global factors, between
+// sparse_llt_kernel phases 1 and 2): one task per wave, 4 waves per
+// workgroup, y in global memory (D.rhs, written by phase 1). The tasks are
+// independent; in the single-workgroup kernel they took ~290 us at N = 256.
+// The kernel stays at this position, behind the prologue, to keep the device
+// code's order (top of the file); a later change may move it next to the tail.
+constexpr int kBorderWaves = 4;
+__global__ void __launch_bounds__(64 * kBorderWaves) border_kernel(SparseDev D) {
+  if (D.flags[kFlagStop]) return;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int32_t *pl = D.plan;
+  const int32_t *clq = pl + D.off[28];
+  const int nc = clq[0], c0 = clq[1], nt0 = nc * (nc + 1) / 2;
+  const int r = lane / 7, c = lane % 7;
+  const bool act49 = lane < 49;
+  const int lane49 = act49 ? lane : 0, r7 = act49 ? r * 7 : 0, c7 = act49 ? c * 7 : 0;
+  const int lane7 = lane < 7 ? lane : 0;
+  double *stg = smem + (size_t)wave * kStageDoubles;
+  double *y = const_cast<double *>(D.rhs);
+  for (int t = blockIdx.x * kBorderWaves + wave; t < nt0; t += gridDim.x * kBorderWaves)
+    border_task<true>(t, nc, c0, pl, D.off, D.L, y, r7, c7, lane49, lane, lane7, act49, stg, D.tail_A, D.tail_ld);
+}
+
 // ---------------------------------------------------------------- host --
 inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -4821,10 +4873,130 @@ int check_args(const m3s_gn_args *a) {
   return M3S_OK;
 }
 
-bool gather_lds_path();  // (knobs, below)
+// Solver knobs: the measured-best defaults, overridable per process by the
+// environment (read ONCE, at the first use) and at run time by m3s_set_knob
+// (bench legs and tests that A/B a path in one process). Each knob is declared
+// once, as a row of one of the two lists below: the values (Knobs), the
+// environment read, set_knob's lookup and its plan-cache drop, and the product
+// build's constants are all derived from the row.
+//   X(name, environment variable or nullptr, default, shapes a plan)
+// The product library carries the knobs of its own paths only; the A/B
+// reference paths (column-task factor, one-workgroup tail, forced dense /
+// one-workgroup solves) and the bounded-wait test hook exist in the test
+// build (-DM3S_TEST_PATHS: libm3s_gn_test.so, tests/conftest.py `test_lib`),
+// and in the product build a test-only knob is its default as a compile-time
+// constant, so no A/B branch reaches the product.
+// Knobs that shape a plan (its schedule, split lists, tail, path) are not all
+// in the plan-cache key: a change drops every cached plan (set_knob), so no
+// launch reads a plan built for another path (e.g. a chip-path plan, cached
+// unscheduled, on the one-workgroup kernel).
+#define M3S_PRODUCT_KNOBS(X)                                                                                           \
+  X(plan_cache, "M3S_PLAN_CACHE", 1, false)   /* 0 = symbolic analysis every call (cold calls, bench.py) */            \
+  X(dense_tail_min, "M3S_DENSE_TAIL_MIN", kDenseTailMin, true) /* smallest top clique solved dense (0: never) */       \
+  X(track_persistent, "M3S_TRACK_PERSISTENT", 1, false) /* 0 = one tracker launch per iteration */                     \
+  X(prologue, "M3S_PROLOGUE", 1, false)       /* 0 = host prepare (ids read back, then the uploads) */
+#define M3S_TEST_KNOBS(X)                                                                                              \
+  X(dense, "M3S_DENSE", 0, true)              /* 1 = dense fallback LLT (only the value 1 counts) */                   \
+  X(cols, "M3S_COLS", 1, true)                /* 0 = large graphs on sparse_llt_kernel's one workgroup */              \
+  X(df, "M3S_DF", 1, true)                    /* 0 = column tasks + border_kernel instead of the dataflow */           \
+  X(tail_cyc, "M3S_TAIL_CYC", 1, true)        /* 0 = the dense tail on one workgroup */                                \
+  X(tail_mfma, "M3S_TAIL_MFMA", 1, true)      /* 0 = the dense tail in sparse_llt_kernel */                            \
+  X(border_split, "M3S_BORDER_SPLIT", 1, true) /* 0 = tail border in the one-workgroup kernel */                       \
+  X(debug_drop_item, nullptr, -1, true)       /* drop one LLT dispatch item (bounded-wait test) */                     \
+  X(gather_lds, nullptr, 1, false)            /* 0 = the round-2 VGPR-staged gathering kernel (bitwise reference) */   \
+  X(tail_pair, "M3S_TAIL_PAIR", 1, false)     /* 0 = tail_cyc_kernel (one tile column per workgroup) */                \
+  X(tail_warm, "M3S_TAIL_WARM", 1, false)     /* 0 = no warm-up of the tail's diagonal factor code */                  \
+  X(gcomb, "M3S_GCOMB", 1, false)             /* 0 = col_backsub_kernel after the tail, not gcol_worker */             \
+  X(gcomb_wg, "M3S_GCOMB_WG", 64, false)      /* gcol_worker workgroups, >= 1 (64 measured best at 128 / 256 KFs) */   \
+  /* the workers pay off once the dense tail's chain is long enough to hide the X_k recursion: 256 KFs                 \
+     (42-column tail) 0.751 -> 0.712 ms per 3-iteration call, 128 KFs (a shorter tail) 0.493 -> 0.501                  \
+     (profiles/r05/solve_ab_gcomb_rotated.txt) */                                                                      \
+  X(gcomb_min_nc, "M3S_GCOMB_MIN_NC", 32, false) /* smallest dense tail (block columns) that takes the workers */
 
-// pack: 0 gathering kernel, 1 gathering kernel that stores the planes,
-// 2 packed kernel (reads the planes; VEC layout only)
+#define M3S_KNOB_ID(name, env, def, shaping) K_##name,
+#define M3S_KNOB_DEF(name, env, def, shaping) {K_##name, #name, env, def, shaping},
+#define M3S_KNOB_DEFAULT(name, env, def, shaping) \
+  case K_##name: return def;
+enum KnobId : int { M3S_PRODUCT_KNOBS(M3S_KNOB_ID) M3S_TEST_KNOBS(M3S_KNOB_ID) };  // = the row's index in kKnobDefs
+struct KnobDef {
+  KnobId id;
+  const char *name, *env;
+  int def;
+  bool shaping;
+};
+constexpr KnobDef kKnobDefs[] = {  // the knobs this build knows by name
+    M3S_PRODUCT_KNOBS(M3S_KNOB_DEF)
+#ifdef M3S_TEST_PATHS
+    M3S_TEST_KNOBS(M3S_KNOB_DEF)
+#endif
+};
+constexpr int kNumKnobs = (int)(sizeof(kKnobDefs) / sizeof(kKnobDefs[0]));
+constexpr bool knob_rows_in_id_order() {
+  for (int k = 0; k < kNumKnobs; k++)
+    if (kKnobDefs[k].id != k) return false;
+  return true;
+}
+static_assert(knob_rows_in_id_order(), "Knobs::v is indexed by KnobId: row k of kKnobDefs is knob k");
+constexpr int knob_default(KnobId k) {
+  switch (k) {
+    M3S_PRODUCT_KNOBS(M3S_KNOB_DEFAULT)
+    M3S_TEST_KNOBS(M3S_KNOB_DEFAULT)
+    default: return 0;
+  }
+}
+#undef M3S_KNOB_ID
+#undef M3S_KNOB_DEF
+#undef M3S_KNOB_DEFAULT
+
+struct Knobs {
+  std::atomic<int> v[kNumKnobs];
+  Knobs() {
+    for (int k = 0; k < kNumKnobs; k++) {
+      v[k] = kKnobDefs[k].def;
+      if (kKnobDefs[k].env)
+        if (const char *e = std::getenv(kKnobDefs[k].env)) v[k] = std::atoi(e);
+    }
+  }
+};
+Knobs &knobs() {
+  static Knobs k;  // thread-safe one-time initialisation
+  return k;
+}
+// A knob's value: the run-time one where this build has the knob, else (a
+// test-only knob in the product build) its default, a compile-time constant.
+template <KnobId K>
+constexpr int knob() {
+  if constexpr (K < kNumKnobs)
+    return knobs().v[K];
+  else
+    return knob_default(K);
+}
+#ifdef M3S_TEST_PATHS
+#define M3S_TEST_KNOB inline
+#else
+#define M3S_TEST_KNOB constexpr
+#endif
+M3S_TEST_KNOB bool cols_path() { return knob<K_cols>() != 0; }
+M3S_TEST_KNOB bool df_path() { return knob<K_df>() != 0; }
+M3S_TEST_KNOB bool tail_cyc() { return knob<K_tail_cyc>() != 0; }
+M3S_TEST_KNOB bool tail_mfma() { return knob<K_tail_mfma>() != 0; }
+M3S_TEST_KNOB bool border_split() { return knob<K_border_split>() != 0; }
+M3S_TEST_KNOB bool force_dense_knob() { return knob<K_dense>() == 1; }
+M3S_TEST_KNOB int drop_item_knob() { return knob<K_debug_drop_item>(); }
+M3S_TEST_KNOB bool gather_lds_path() { return knob<K_gather_lds>() != 0; }
+M3S_TEST_KNOB bool tail_pair_path() { return knob<K_tail_pair>() != 0; }
+M3S_TEST_KNOB bool tail_warm_knob() { return knob<K_tail_warm>() != 0; }
+M3S_TEST_KNOB bool gcomb_knob() { return knob<K_gcomb>() != 0; }
+M3S_TEST_KNOB int gcomb_wg_knob() { return std::max(1, knob<K_gcomb_wg>()); }
+M3S_TEST_KNOB int gcomb_min_nc_knob() { return knob<K_gcomb_min_nc>(); }
+#undef M3S_TEST_KNOB
+#ifndef M3S_TEST_PATHS
+static_assert(cols_path() && df_path() && !force_dense_knob() && gcomb_wg_knob() == 64,
+              "product build: the test-only knobs are constants");
+#endif
+inline int dense_tail_min() { return knob<K_dense_tail_min>(); }
+inline bool plan_cache_enabled() { return knob<K_plan_cache>() != 0; }
+
 // In-call timing (m3s_debug_call_timing): the drop-in call sets a start /
 // stop event pair for its next linearize launch, which then goes through
 // hipExtLaunchKernel: the events take the dispatch's own begin / end
@@ -4849,6 +5021,8 @@ void launch_lin(K kernel, dim3 g, dim3 b, hipStream_t st, const LinArgs &L) {
   }
 }
 
+// pack: 0 gathering kernel, 1 gathering kernel that stores the planes,
+// 2 packed kernel (reads the planes; VEC layout only)
 template <int MODE, bool TRACK>
 int launch_linearize(const LinArgs &L, int64_t blocks, bool vec, int pack, hipStream_t st) {
   if (blocks <= 0) return M3S_OK;
@@ -4892,120 +5066,6 @@ int read_K(const float *K, ResidualParams &P, hipStream_t st) {
   P.fx = k[0], P.fy = k[4], P.cx = k[2], P.cy = k[5];
   return M3S_OK;
 }
-
-// Host registry of the per-call plan (keyed by workspace): the stepwise API
-// calls prepare and solve separately.
-// smallest top clique solved as a dense tail (M3S_DENSE_TAIL_MIN overrides;
-// 0 disables it)
-// Dense-tail border updates spread over the chip (global factors, between
-// sparse_llt_kernel phases 1 and 2): one task per wave, 4 waves per
-// workgroup, y in global memory (D.rhs, written by phase 1). The tasks are
-// independent; in the single-workgroup kernel they took ~290 us at N = 256.
-constexpr int kBorderWaves = 4;
-__global__ void __launch_bounds__(64 * kBorderWaves) border_kernel(SparseDev D) {
-  if (D.flags[kFlagStop]) return;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int32_t *pl = D.plan;
-  const int32_t *clq = pl + D.off[28];
-  const int nc = clq[0], c0 = clq[1], nt0 = nc * (nc + 1) / 2;
-  const int r = lane / 7, c = lane % 7;
-  const bool act49 = lane < 49;
-  const int lane49 = act49 ? lane : 0, r7 = act49 ? r * 7 : 0, c7 = act49 ? c * 7 : 0;
-  const int lane7 = lane < 7 ? lane : 0;
-  double *stg = smem + (size_t)wave * kStageDoubles;
-  double *y = const_cast<double *>(D.rhs);
-  for (int t = blockIdx.x * kBorderWaves + wave; t < nt0; t += gridDim.x * kBorderWaves)
-    border_task<true>(t, nc, c0, pl, D.off, D.L, y, r7, c7, lane49, lane, lane7, act49, stg, D.tail_A, D.tail_ld);
-}
-
-// Solver knobs: the measured-best defaults, overridable per process by the
-// environment (read ONCE, at the first solve) and at run time by
-// m3s_set_knob (bench legs and tests that A/B a path in one process). The
-// product library carries the knobs of its own paths only; the A/B reference
-// paths (column-task factor, one-workgroup tail, forced dense / one-workgroup
-// solves) and the bounded-wait test hook exist in the test build
-// (-DM3S_TEST_PATHS: libm3s_gn_test.so, tests/conftest.py `test_lib`).
-struct Knobs {
-  std::atomic<int> plan_cache{1};      // M3S_PLAN_CACHE: 0 = symbolic analysis every call (cold calls)
-  std::atomic<int> dense_tail_min{kDenseTailMin};  // M3S_DENSE_TAIL_MIN: smallest dense tail (0: never)
-  std::atomic<int> track_persistent{1};  // M3S_TRACK_PERSISTENT: 0 = one tracker launch per iteration
-  std::atomic<int> prologue{1};        // M3S_PROLOGUE: 0 = host prepare (ids read back, then the uploads)
-#ifdef M3S_TEST_PATHS
-  std::atomic<int> dense{0};           // M3S_DENSE: 1 = dense fallback LLT
-  std::atomic<int> cols{1};            // M3S_COLS: 0 = large graphs on sparse_llt_kernel's one workgroup
-  std::atomic<int> df{1};              // M3S_DF: 0 = column tasks + border_kernel instead of the dataflow
-  std::atomic<int> tail_cyc{1};        // M3S_TAIL_CYC: 0 = the dense tail on one workgroup
-  std::atomic<int> tail_mfma{1};       // M3S_TAIL_MFMA: 0 = the dense tail in sparse_llt_kernel
-  std::atomic<int> border_split{1};    // M3S_BORDER_SPLIT: 0 = tail border in the one-workgroup kernel
-  std::atomic<int> debug_drop_item{-1};  // drop one LLT dispatch item (bounded-wait test)
-  std::atomic<int> gather_lds{1};      // 0: the round-2 VGPR-staged gathering kernel (bitwise reference)
-  std::atomic<int> tail_pair{1};       // 0: tail_cyc_kernel (one tile column per workgroup)
-  std::atomic<int> tail_warm{1};       // 0: no warm-up of the tail's diagonal factor code
-  std::atomic<int> gcomb{1};           // 0: col_backsub_kernel after the tail instead of gcol_worker
-  std::atomic<int> gcomb_wg{64};       // gcol_worker workgroups (at most; 64 measured best at 128 / 256 KFs)
-  std::atomic<int> gcomb_min_nc{32};   // smallest dense tail (block columns) that takes the workers
-#endif
-  Knobs() {
-    auto env = [](const char *name, std::atomic<int> &v) {
-      if (const char *e = std::getenv(name)) v = std::atoi(e);
-    };
-    env("M3S_PLAN_CACHE", plan_cache);
-    env("M3S_DENSE_TAIL_MIN", dense_tail_min);
-    env("M3S_TRACK_PERSISTENT", track_persistent);
-    env("M3S_PROLOGUE", prologue);
-#ifdef M3S_TEST_PATHS
-    env("M3S_DENSE", dense);
-    env("M3S_COLS", cols);
-    env("M3S_DF", df);
-    env("M3S_TAIL_CYC", tail_cyc);
-    env("M3S_TAIL_MFMA", tail_mfma);
-    env("M3S_BORDER_SPLIT", border_split);
-    env("M3S_TAIL_PAIR", tail_pair);
-    env("M3S_TAIL_WARM", tail_warm);
-    env("M3S_GCOMB", gcomb);
-    env("M3S_GCOMB_WG", gcomb_wg);
-    env("M3S_GCOMB_MIN_NC", gcomb_min_nc);
-#endif
-  }
-};
-Knobs &knobs() {
-  static Knobs k;  // thread-safe one-time initialisation
-  return k;
-}
-#ifdef M3S_TEST_PATHS
-inline bool cols_path() { return knobs().cols != 0; }
-inline bool df_path() { return knobs().df != 0; }
-inline bool tail_cyc() { return knobs().tail_cyc != 0; }
-inline bool tail_mfma() { return knobs().tail_mfma != 0; }
-inline bool border_split() { return knobs().border_split != 0; }
-inline bool force_dense_knob() { return knobs().dense == 1; }
-inline int drop_item_knob() { return knobs().debug_drop_item; }
-bool gather_lds_path() { return knobs().gather_lds != 0; }
-inline bool tail_pair_path() { return knobs().tail_pair != 0; }
-inline bool tail_warm_knob() { return knobs().tail_warm != 0; }
-inline bool gcomb_knob() { return knobs().gcomb != 0; }
-inline int gcomb_wg_knob() { return std::max(1, knobs().gcomb_wg.load()); }
-inline int gcomb_min_nc_knob() { return knobs().gcomb_min_nc.load(); }
-#else
-constexpr bool cols_path() { return true; }
-constexpr bool df_path() { return true; }
-constexpr bool tail_cyc() { return true; }
-constexpr bool tail_mfma() { return true; }
-constexpr bool border_split() { return true; }
-constexpr bool force_dense_knob() { return false; }
-constexpr int drop_item_knob() { return -1; }
-bool gather_lds_path() { return true; }
-constexpr bool tail_pair_path() { return true; }
-constexpr bool tail_warm_knob() { return true; }
-constexpr bool gcomb_knob() { return true; }
-constexpr int gcomb_wg_knob() { return 64; }
-// the workers pay off once the dense tail's chain is long enough to hide the
-// X_k recursion: 256 KFs (42-column tail) 0.751 -> 0.712 ms per 3-iteration
-// call, 128 KFs (a shorter tail) 0.493 -> 0.501 (profiles/r05/solve_ab_gcomb_rotated.txt)
-constexpr int gcomb_min_nc_knob() { return 32; }
-#endif
-inline int dense_tail_min() { return knobs().dense_tail_min; }
 
 struct PlanMeta {
   int epoch = 0;  // solve launches since m3s_gn_prepare (column-task flags / tickets)
@@ -5061,6 +5121,8 @@ PlanMeta solve_view(const PlanMeta &M) {
   v.plan_pending = M.plan_pending;
   return v;
 }
+// Host registry of the per-call plan (keyed by workspace): the stepwise API
+// calls prepare and solve separately.
 std::mutex g_reg_mu;
 std::unordered_map<const void *, PlanMeta> g_reg;
 
@@ -5145,7 +5207,460 @@ void build_eorder(const std::vector<int32_t> &rj, int64_t eb, int64_t E_loc, std
   std::stable_sort(out.begin(), out.end(), [&](int32_t x, int32_t y) { return rj[eb + x] < rj[eb + y]; });
 }
 
-int host_finish(const m3s_gn_args *a, hipStream_t st);
+constexpr size_t kMaxLdsBytes = 150 * 1024;
+// Defined behind gn_solve_impl: its body names the sparse_llt_kernel
+// specialisations, and where a kernel template is first named decides its
+// place in the device code (the order rule, m3s_gn.hip).
+void set_lds_attributes_once();
+
+// Host symbolic plans of recent edge sets (the same factor graph is usually
+// solved many times: every keyframe's local/global optimisation, every bench
+// step). Keyed by (N, HW, E, dense override, remapped ranks).
+struct PlanCacheEntry {
+  int64_t N = 0, HW = 0, E = 0;
+  bool dense = false;
+  int tail_min = 0;  // dense_tail_min() the plan was built with
+  std::vector<int32_t> ri, rj;
+  PlanMeta meta;
+};
+std::mutex g_cache_mu;
+std::vector<PlanCacheEntry> g_cache;  // most recent first
+constexpr size_t kPlanCacheSize = 4;
+
+// m3s_set_knob: the previous value, or -(1 << 30) for a name this build does
+// not know. A plan-shaping knob set to a different value drops the plan cache.
+int set_knob(const char *name, int value) {
+  Knobs &K = knobs();
+  for (int k = 0; k < kNumKnobs; k++)
+    if (std::strcmp(kKnobDefs[k].name, name) == 0) {
+      const int old = K.v[k].exchange(value);
+      if (kKnobDefs[k].shaping && old != value) {
+        std::lock_guard<std::mutex> g(g_cache_mu);
+        g_cache.clear();
+      }
+      return old;
+    }
+  return -(1 << 30);
+}
+
+// Symbolic plan + LDS budget + full-range task table for remapped ranks.
+PlanMeta build_plan_meta(const m3s_gn_args *a, const Layout &Ly, const std::vector<int32_t> &ri,
+                         const std::vector<int32_t> &rj, bool force_dense) {
+  PlanMeta meta;
+  const int64_t E = a->E;
+  if (a->N > 1) {
+    SparsePlan P;
+    // The dispatch schedule (witems) and the split update lists (PART items)
+    // serve only the one-workgroup sparse_llt_kernel; a factor in global
+    // memory on the chip-wide path (df_factor / tail / column back-
+    // substitution) needs neither: at 256 KFs that halves the host analysis.
+    build_sparse_plan((int)a->N, ri, rj, P, 0, 0, dense_tail_min(), false);
+    const bool global_factor = sizeof(double) * ((size_t)(P.S + P.m) * 49 + (size_t)P.m * 7) > kMaxLdsBytes;
+    const bool chip_path = global_factor && cols_path() && P.m <= 512 && (P.nc == 0 || 7 * P.nc + 1 <= 16 * kTailMaxT);
+    if (global_factor && !chip_path)  // split long update lists for the staged global-factor products
+      build_sparse_plan((int)a->N, ri, rj, P, kSplitUpdates, Ly.slot_cap - 1, dense_tail_min(), true);
+    else if (!chip_path)
+      schedule_plan_items(P);
+    PlanImage img;
+    flatten_plan(P, img);
+    // df_factor_kernel's dispatch list: the sparse columns in level order,
+    // DIAG(k) then the OFF tasks of column k, then the dense-tail border tasks
+    meta.off_dfitems = (int)img.data.size();
+    for (int32_t k : P.corder) {
+      img.data.push_back(-1 - k);
+      for (int q = 0; q < P.col_ptr[k + 1] - P.col_ptr[k]; q++) img.data.push_back(P.ctask0[k] + q);
+    }
+    meta.n_dfsparse = (int)img.data.size() - meta.off_dfitems;
+    for (int b = 0; b < P.nc * (P.nc + 1) / 2; b++) img.data.push_back((int32_t)P.task_dst.size() + b);
+    meta.n_dfitems = (int)img.data.size() - meta.off_dfitems;
+    const bool fits = (int64_t)img.data.size() <= Ly.plan_cap && P.S <= Ly.slot_cap;
+    if (fits && !force_dense) {
+      meta.sparse = true;
+      meta.m = P.m;
+      meta.S = P.S;
+      meta.levels = P.levels;
+      meta.plan_len = (int)img.data.size();
+      meta.n_items = (int)P.items.size();
+      meta.n_tasks = (int)P.task_dst.size();
+      meta.n_parts = (int)P.part_q0.size();
+      meta.nc = P.nc;
+      meta.nnz = P.col_ptr.empty() ? 0 : P.col_ptr[P.m];
+      // LDS plan of sparse_llt_kernel<STORE>: flags always, factor + W + y if
+      // they fit, the plan too if it fits as well; else global factor with
+      // per-wave stage areas
+      const size_t flags_bytes =
+          sizeof(int32_t) * (((size_t)(P.S + 2 * P.m + P.part_q0.size()) + 1) & ~size_t(1));
+      const size_t fac_bytes = sizeof(double) * ((size_t)(P.S + P.m) * 49 + (size_t)P.m * 7);
+      const size_t plan_bytes = sizeof(int32_t) * ((img.data.size() + 1) & ~size_t(1));
+      const size_t stage_bytes = sizeof(double) * 16 * (size_t)kStageDoubles;
+      const size_t fin_bytes = sizeof(double) * kFin * (size_t)E;
+      if (fac_bytes + plan_bytes + flags_bytes <= kMaxLdsBytes) {
+        meta.store = 1;
+        meta.lds_bytes = fac_bytes + plan_bytes + flags_bytes;
+      } else if (fac_bytes + flags_bytes <= kMaxLdsBytes) {
+        meta.store = 2;
+        meta.lds_bytes = fac_bytes + flags_bytes;
+      }
+      if (meta.store != 0 && meta.lds_bytes + fin_bytes <= kMaxLdsBytes) {
+        meta.asm_lds = true;
+        meta.lds_bytes += fin_bytes;
+      }
+      if (meta.store == 0) {
+        meta.store = 0;
+        meta.lds_bytes = sizeof(double) * (size_t)P.m * 7 + flags_bytes + stage_bytes;
+        if (meta.lds_bytes > kMaxLdsBytes) meta.sparse = false;  // dense fallback
+      }
+      meta.h_plan = std::move(img.data);
+      img.data.clear();
+      meta.img = img;
+    }
+  }
+  (void)E;
+  return meta;
+}
+
+// The per-call flag state the solve kernels of a plan rely on: the column-
+// task / dataflow / dense-tail epoch flags live only on the global-factor
+// path (the LDS-resident factors keep theirs in LDS), and no tagged granule
+// of an earlier call may match this call's epochs.
+bool reset_plan_flags(const PlanMeta &M, const Layout &Ly, void *ws, hipStream_t st) {
+  bool ok = true;
+  if (!(M.sparse && M.store != 0))
+    ok &= hipMemsetAsync(at<int32_t>(ws, Ly.colsync), 0, Ly.tail - Ly.colsync, st) == hipSuccess;
+  if (M.nc > 0)
+    ok &= hipMemsetAsync(at<double>(ws, Ly.tail) + tail_gran_offset_doubles(), 0,
+                         sizeof(double) * (tail_scratch_doubles() - tail_gran_offset_doubles()), st) == hipSuccess;
+  return ok;
+}
+
+// Upload a plan on the device's side stream and make `st` wait for it: the
+// copy runs while the first linearize kernel does instead of queueing behind
+// it. Callers have waited for every earlier launch on `st` (the prologue's
+// event or a stream sync), so nothing still running there reads `dst`.
+bool upload_plan(Staging *SG, PlanMeta &M, char *dst, hipStream_t st) {
+  if (!(M.sparse && !M.h_plan.empty())) return true;
+  const size_t nb = sizeof(int32_t) * M.h_plan.size();
+  if (SG->plan_pending && hipEventSynchronize(SG->plan_ev) != hipSuccess) return false;
+  SG->plan_pending = false;
+  if (!pinned_reserve(SG->plan_up, SG->plan_cap, nb)) return false;
+  memcpy(SG->plan_up, M.h_plan.data(), nb);
+  bool ok = hipMemcpyAsync(dst, SG->plan_up, nb, hipMemcpyHostToDevice, SG->side) == hipSuccess;
+  ok &= hipEventRecord(SG->plan_ev, SG->side) == hipSuccess;
+  ok &= hipStreamWaitEvent(st, SG->plan_ev, 0) == hipSuccess;
+  SG->plan_pending = ok;
+  return ok;
+}
+
+// Test hook for the bounded waits (tests/test_gpu_backend.py, knob
+// debug_drop_item): drop one item of sparse_llt_kernel's dispatch list, so the
+// items that read its blocks wait on a flag that is never set; the waits time
+// out and the iteration ends as a solve failure (dx = 0) instead of hanging.
+// On the chip-wide path (global factor) the item is dropped from
+// df_factor_kernel's dispatch list instead.
+void apply_drop_item(PlanMeta &M) {
+  const int d = drop_item_knob();
+  if (d < 0 || !M.sparse || M.h_plan.empty()) return;
+  if (M.store == 0 && M.n_dfitems > 0) {
+    int32_t *di = M.h_plan.data() + M.off_dfitems;
+    if (d < M.n_dfitems) {
+      for (int t = d; t + 1 < M.n_dfitems; t++) di[t] = di[t + 1];
+      M.n_dfitems -= 1;
+    }
+    return;
+  }
+  if (M.img.off_wave_ptr >= (int64_t)M.h_plan.size()) return;
+  int32_t *wp = M.h_plan.data() + M.img.off_wave_ptr, *wi = M.h_plan.data() + M.img.off_witems;
+  if (d < wp[1]) {
+    for (int t = d; t + 1 < wp[1]; t++) wi[t] = wi[t + 1];
+    wp[1] -= 1;
+  }
+}
+
+// The host prepare, per solve call (the reference's _unique / searchsorted
+// also synchronise): read ii/jj (+ K) once — the call's only host sync — rank the
+// ids, fetch the plan (or defer it to the first solve) and enqueue ONE
+// upload of everything the launches read (pinned staging, above).
+int gn_prepare_impl(const m3s_gn_args *a, hipStream_t st) {
+  const Layout Ly = gn_layout(a->N, a->HW, a->E);
+  void *ws = a->workspace;
+  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
+  Staging *SG = stage_for_device();
+  if (!SG) return M3S_ELAUNCH;
+  if (SG->pending && hipEventSynchronize(SG->ev) != hipSuccess) return M3S_ELAUNCH;
+  SG->pending = false;
+  const int64_t E = a->E;
+  if (!pinned_reserve(SG->down, SG->down_cap, 64 + 2 * sizeof(int64_t) * (size_t)E)) return M3S_ELAUNCH;
+  float *hK = reinterpret_cast<float *>(SG->down);  // calib intrinsics, read with ii/jj
+  int64_t *hii = reinterpret_cast<int64_t *>(SG->down + 64), *hjj = hii + E;
+  for (int q = 0; q < 9; q++) hK[q] = 0.f;
+  if (a->mode == M3S_MODE_CALIB &&
+      hipMemcpyAsync(hK, a->K, sizeof(float) * 9, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return M3S_ELAUNCH;
+  if (a->N > 1 && a->dx_out && hipMemsetAsync(a->dx_out, 0, sizeof(float) * 7 * (a->N - 1), st) != hipSuccess)
+    return M3S_ELAUNCH;
+  if (E > 0 && hipMemcpyAsync(hii, a->ii, sizeof(int64_t) * E, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return M3S_ELAUNCH;
+  if (E > 0 && hipMemcpyAsync(hjj, a->jj, sizeof(int64_t) * E, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return M3S_ELAUNCH;
+  if (hipStreamSynchronize(st) != hipSuccess) return M3S_ELAUNCH;
+  std::vector<int32_t> ri, rj;
+  const int nu = host_remap(hii, hjj, E, ri, rj);
+  const bool bad = nu > a->N;
+  const bool force_dense = force_dense_knob();
+  PlanMeta meta;
+  bool hit = false;
+  if (!bad && plan_cache_enabled()) {
+    std::lock_guard<std::mutex> g(g_cache_mu);
+    for (size_t q = 0; q < g_cache.size(); q++) {
+      const PlanCacheEntry &C = g_cache[q];
+      if (C.N == a->N && C.HW == a->HW && C.E == E && C.dense == force_dense &&
+          C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
+        meta = C.meta;
+        std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
+        hit = true;
+        break;
+      }
+    }
+  }
+  if (hit && E > 0 && meta.eorder.empty()) build_eorder(meta.rj, 0, E, meta.eorder);  // cached by the prologue path
+  if (!hit) {
+    // ranks and the full-range task table now (the first linearize needs
+    // them); the symbolic plan is built by the first solve of this call,
+    // while the first linearize kernel runs (finish_plan)
+    meta.h_ri = ri;
+    meta.rj = rj;
+    if (E > 0) build_eorder(meta.rj, 0, E, meta.eorder);
+    meta.sparse = !bad && !force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
+    meta.plan_pending = !bad && a->N > 1;
+    meta.force_dense = force_dense;
+  }
+  for (int q = 0; q < 8; q++) meta.h_info[q] = 0;
+  for (int q = 0; q < 64; q++) meta.h_flags[q] = 0;
+  meta.h_info[M3S_INFO_N_UNIQUE] = nu;
+  if (bad) meta.h_info[M3S_INFO_BAD_EDGE] = 1, meta.h_flags[kFlagStop] = 1;
+  if (a->mode == M3S_MODE_CALIB) {  // K row-major: fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]
+    meta.has_K = true;
+    meta.K4[0] = hK[0], meta.K4[1] = hK[4], meta.K4[2] = hK[2], meta.K4[3] = hK[5];
+  }
+  meta.planes_ok = false;
+  meta.range_b = 0, meta.range_e = E, meta.order_ok = E > 0;
+  if (meta.sparse && !meta.plan_pending && meta.lds_bytes > 64 * 1024) set_lds_attributes_once();
+  std::lock_guard<std::mutex> g(g_reg_mu);
+  PlanMeta &M = g_reg[ws];
+  M = std::move(meta);
+  bool ok = true;
+  if (!M.plan_pending) ok &= reset_plan_flags(M, Ly, ws, st);
+  M.epoch = 0;
+  if (!M.plan_pending) apply_drop_item(M);
+  // one upload: flags | rank_i | rank_j | edge counters | edge order [| plan] (the
+  // layout keeps them in this order), then info (the caller's tensor) from
+  // the same buffer
+  const bool with_plan = M.sparse && !M.plan_pending && !M.h_plan.empty();
+  const bool with_tasks = E > 0;
+  size_t n_up = with_plan ? Ly.plan - Ly.flags + sizeof(int32_t) * M.h_plan.size()
+                          : with_tasks ? Ly.eorder - Ly.flags + sizeof(int32_t) * M.eorder.size()
+                                       : Ly.edge_cnt - Ly.flags + edge_cnt_bytes(E);
+  n_up = align_up(n_up, 16);
+  if (!pinned_reserve(SG->up, SG->up_cap, n_up + sizeof M.h_info)) return M3S_ELAUNCH;
+  char *up = SG->up;
+  memcpy(up, M.h_flags, sizeof M.h_flags);
+  memset(up + (Ly.edge_cnt - Ly.flags), 0, edge_cnt_bytes(E));  // the fused finalize's counters
+  if (E > 0) {
+    memcpy(up + (Ly.rank_i - Ly.flags), M.h_ri.data(), sizeof(int32_t) * E);
+    memcpy(up + (Ly.rank_j - Ly.flags), M.rj.data(), sizeof(int32_t) * E);
+  }
+  if (with_tasks) memcpy(up + (Ly.eorder - Ly.flags), M.eorder.data(), sizeof(int32_t) * M.eorder.size());
+  if (with_plan) memcpy(up + (Ly.plan - Ly.flags), M.h_plan.data(), sizeof(int32_t) * M.h_plan.size());
+  memcpy(up + n_up, M.h_info, sizeof M.h_info);
+  ok &= hipMemcpyAsync(at<char>(ws, Ly.flags), up, n_up, hipMemcpyHostToDevice, st) == hipSuccess;
+  ok &= hipMemcpyAsync(a->info, up + n_up, sizeof M.h_info, hipMemcpyHostToDevice, st) == hipSuccess;
+  ok &= hipEventRecord(SG->ev, st) == hipSuccess;
+  SG->pending = ok;
+  return ok ? M3S_OK : M3S_ELAUNCH;
+}
+
+// The deferred half of a cold prepare: the symbolic plan (ordering, fill,
+// update lists; build_plan_meta) on the host, its upload, and the per-plan
+// flag resets. Called by a call's first solve, i.e. after its first
+// linearize is on the stream: the analysis runs while that kernel does.
+int finish_plan(const m3s_gn_args *a, const Layout &Ly, hipStream_t st) {
+  void *ws = a->workspace;
+  std::vector<int32_t> ri, rj;
+  bool force_dense;
+  {
+    std::lock_guard<std::mutex> g(g_reg_mu);
+    auto it = g_reg.find(ws);
+    if (it == g_reg.end()) return M3S_EINVAL;
+    if (!it->second.plan_pending) return M3S_OK;
+    ri = it->second.h_ri;
+    rj = it->second.rj;
+    force_dense = it->second.force_dense;
+  }
+  PlanMeta built = build_plan_meta(a, Ly, ri, rj, force_dense);
+  if (built.sparse && built.lds_bytes > 64 * 1024) set_lds_attributes_once();
+  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
+  Staging *SG = stage_for_device();
+  if (!SG) return M3S_ELAUNCH;
+  if (SG->plan_pending && hipEventSynchronize(SG->plan_ev) != hipSuccess) return M3S_ELAUNCH;
+  SG->plan_pending = false;
+  std::lock_guard<std::mutex> g(g_reg_mu);
+  PlanMeta &M = g_reg[ws];
+  M.sparse = built.sparse, M.store = built.store, M.asm_lds = built.asm_lds, M.lds_bytes = built.lds_bytes;
+  M.m = built.m, M.S = built.S, M.levels = built.levels, M.plan_len = built.plan_len;
+  M.n_items = built.n_items, M.n_tasks = built.n_tasks, M.n_parts = built.n_parts, M.nc = built.nc;
+  M.off_dfitems = built.off_dfitems, M.n_dfitems = built.n_dfitems, M.nnz = built.nnz;
+  M.n_dfsparse = built.n_dfsparse;
+  M.img = built.img;
+  M.h_plan = std::move(built.h_plan);
+  M.plan_pending = false;
+  if (plan_cache_enabled()) {
+    PlanCacheEntry C;
+    C.N = a->N, C.HW = a->HW, C.E = a->E, C.dense = force_dense, C.ri = ri, C.rj = rj;
+    C.tail_min = dense_tail_min();
+    C.meta = M;
+    std::lock_guard<std::mutex> gc(g_cache_mu);
+    g_cache.insert(g_cache.begin(), std::move(C));
+    if (g_cache.size() > kPlanCacheSize) g_cache.pop_back();
+  }
+  bool ok = reset_plan_flags(M, Ly, ws, st);
+  apply_drop_item(M);
+  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
+  return ok ? M3S_OK : M3S_ELAUNCH;
+}
+
+// The host half of an async prepare (gn_prepare_async), at the first point a
+// call needs its ids on the host (its first solve, or a sharded rank's edge
+// range): wait for the prologue (normally long done: the first linearize is
+// queued behind it), read ii / jj / K from the pinned slot, rank the ids on
+// the host (the plan and its cache key need them), and fetch the cached plan;
+// a miss leaves the plan to finish_plan. The linearize state of the entry
+// (range, task table, planes) is the prologue's and stays.
+int host_finish(const m3s_gn_args *a, hipStream_t st) {
+  void *ws = a->workspace;
+  int slot = -1;
+  {
+    std::lock_guard<std::mutex> g(g_reg_mu);
+    auto it = g_reg.find(ws);
+    if (it == g_reg.end()) return M3S_EINVAL;
+    if (!it->second.host_pending) return M3S_OK;
+    slot = it->second.slot;
+  }
+  const int64_t E = a->E;
+  std::vector<int64_t> hii((size_t)E), hjj((size_t)E);
+  float hK[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  {
+    std::lock_guard<std::mutex> stage_lock(g_stage_mu);
+    Staging *SG = stage_for_device();
+    if (!SG || slot < 0 || slot >= (int)SG->slots.size()) return M3S_ELAUNCH;
+    DownSlot &D = SG->slots[slot];
+    if (hipEventSynchronize(D.ev) != hipSuccess) return M3S_ELAUNCH;
+    if (a->mode == M3S_MODE_CALIB) memcpy(hK, D.p, sizeof hK);
+    if (E > 0) {
+      memcpy(hii.data(), D.p + 64, sizeof(int64_t) * (size_t)E);
+      memcpy(hjj.data(), D.p + 64 + sizeof(int64_t) * (size_t)E, sizeof(int64_t) * (size_t)E);
+    }
+    D.busy = false;
+  }
+  std::vector<int32_t> ri, rj;
+  const int nu = host_remap(hii.data(), hjj.data(), E, ri, rj);
+  const bool bad = nu > a->N;  // the prologue has stopped the call (flags, info)
+  const Layout Ly = gn_layout(a->N, a->HW, a->E);
+  bool force_dense;
+  {
+    std::lock_guard<std::mutex> g(g_reg_mu);
+    force_dense = g_reg.at(ws).force_dense;
+  }
+  PlanMeta hitm;
+  bool hit = false;
+  if (!bad && plan_cache_enabled()) {
+    std::lock_guard<std::mutex> g(g_cache_mu);
+    for (size_t q = 0; q < g_cache.size(); q++) {
+      const PlanCacheEntry &C = g_cache[q];
+      if (C.N == a->N && C.HW == a->HW && C.E == E && C.dense == force_dense &&
+          C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
+        hitm = C.meta;
+        std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
+        hit = true;
+        break;
+      }
+    }
+  }
+  if (hit && hitm.sparse && hitm.lds_bytes > 64 * 1024) set_lds_attributes_once();
+  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
+  Staging *SG = stage_for_device();
+  if (!SG) return M3S_ELAUNCH;
+  std::lock_guard<std::mutex> g(g_reg_mu);
+  PlanMeta &M = g_reg[ws];
+  M.host_pending = false, M.slot = -1;
+  M.h_ri = std::move(ri), M.rj = std::move(rj);
+  M.K4[0] = hK[0], M.K4[1] = hK[4], M.K4[2] = hK[2], M.K4[3] = hK[5];
+  if (bad) {
+    M.sparse = false, M.plan_pending = false;
+    return M3S_OK;
+  }
+  if (!hit) return M3S_OK;  // plan_pending: finish_plan builds it
+  M.sparse = hitm.sparse, M.store = hitm.store, M.asm_lds = hitm.asm_lds, M.lds_bytes = hitm.lds_bytes;
+  M.m = hitm.m, M.S = hitm.S, M.levels = hitm.levels, M.plan_len = hitm.plan_len;
+  M.n_items = hitm.n_items, M.n_tasks = hitm.n_tasks, M.n_parts = hitm.n_parts, M.nc = hitm.nc;
+  M.off_dfitems = hitm.off_dfitems, M.n_dfitems = hitm.n_dfitems, M.nnz = hitm.nnz;
+  M.n_dfsparse = hitm.n_dfsparse;
+  M.img = hitm.img;
+  M.h_plan = std::move(hitm.h_plan);
+  M.plan_pending = false;
+  bool ok = reset_plan_flags(M, Ly, ws, st);
+  apply_drop_item(M);
+  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
+  return ok ? M3S_OK : M3S_ELAUNCH;
+}
+
+// Prepare a call without a host round trip: one prologue kernel on the stream
+// (ranks, task table, flags, info, dx_out; the ids to pinned memory) and the
+// registry entry; the host reads the ids later (host_finish), while the first
+// linearize runs. Large edge sets (> kProMaxE) take the synchronous prepare.
+int gn_prepare_async(const m3s_gn_args *a, hipStream_t st) {
+  const int64_t E = a->E;
+  if (E > kProMaxE || a->N > (int64_t)1 << 30 || knob<K_prologue>() == 0) return gn_prepare_impl(a, st);
+  const Layout Ly = gn_layout(a->N, a->HW, E);
+  void *ws = a->workspace;
+  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
+  Staging *SG = stage_for_device();
+  if (!SG) return M3S_ELAUNCH;
+  const int slot = acquire_slot(*SG, 64 + 2 * sizeof(int64_t) * (size_t)E);
+  if (slot < 0) return M3S_ELAUNCH;
+  DownSlot &D = SG->slots[slot];
+  ProArgs P;
+  P.ii = a->ii, P.jj = a->jj;
+  P.K = a->mode == M3S_MODE_CALIB ? a->K : nullptr;
+  P.down_K = reinterpret_cast<float *>(D.dp);
+  P.down_ii = reinterpret_cast<int64_t *>(D.dp + 64);
+  P.down_jj = P.down_ii + E;
+  P.E = (int)E, P.N = (int)a->N, P.P2 = prologue_p2(E);
+  P.flags = at<int32_t>(ws, Ly.flags), P.rank_i = at<int32_t>(ws, Ly.rank_i), P.rank_j = at<int32_t>(ws, Ly.rank_j);
+  P.eorder = at<int32_t>(ws, Ly.eorder), P.info = a->info, P.edge_cnt = at<uint32_t>(ws, Ly.edge_cnt);
+  P.dx_out = a->dx_out;
+  P.n_dx = (a->N > 1 && a->dx_out) ? (int)(7 * (a->N - 1)) : 0;
+  const size_t lds = prologue_lds(P.E, P.P2);
+  if (lds > 64 * 1024) set_lds_attributes_once();
+  gn_prologue_kernel<<<1, kProThreads, lds, st>>>(P);
+  if (launch_ok() != M3S_OK || hipEventRecord(D.ev, st) != hipSuccess) {
+    D.busy = false;
+    return M3S_ELAUNCH;
+  }
+  PlanMeta meta;
+  meta.host_pending = true, meta.slot = slot;
+  meta.has_K = a->mode == M3S_MODE_CALIB;
+  meta.force_dense = force_dense_knob();
+  meta.sparse = !meta.force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
+  meta.plan_pending = a->N > 1;
+  meta.range_b = 0, meta.range_e = E, meta.order_ok = E > 0;
+  std::lock_guard<std::mutex> g(g_reg_mu);
+  PlanMeta &M = g_reg[ws];
+  if (M.host_pending && M.slot >= 0 && M.slot < (int)SG->slots.size() && M.slot != slot)
+    SG->slots[M.slot].busy = false;  // a re-prepare of a workspace whose ids were never read
+  M = std::move(meta);
+  M.epoch = 0;
+  return M3S_OK;
+}
 
 int gn_linearize_impl(const m3s_gn_args *a, const ResidualParams &P, int64_t eb, int64_t ee,
                       double *edge_sums, hipStream_t st, bool fuse_fin = false, int64_t *chunks_used = nullptr) {
@@ -5261,13 +5776,8 @@ int gn_linearize_impl(const m3s_gn_args *a, const ResidualParams &P, int64_t eb,
   return rc;  // NULL edge_sums: partials only (kernel timing)
 }
 
-constexpr size_t kMaxLdsBytes = 150 * 1024;
-int finish_plan(const m3s_gn_args *a, const Layout &Ly, hipStream_t st);
-void set_lds_attributes_once();
-
 // edge_sums: per-edge local sums (stepwise API), or NULL with `partials` of
 // `chunks` chunks per edge (single-GPU call: no separate reduce launch).
-
 int gn_solve_impl(const m3s_gn_args *a, const double *edge_sums, const float *partials, int64_t chunks,
                   hipStream_t st, bool fin_ready = false) {
   const Layout Ly = gn_layout(a->N, a->HW, a->E);
@@ -5547,25 +6057,6 @@ int gn_solve_impl(const m3s_gn_args *a, const double *edge_sums, const float *pa
   return launch_ok();
 }
 
-// Per call: zero state, bring ii/jj to the host (the reference's _unique /
-// searchsorted also synchronise), rank them, build and upload the sparse plan.
-// Host symbolic plans of recent edge sets (the same factor graph is usually
-// solved many times: every keyframe's local/global optimisation, every bench
-// step). Keyed by (N, HW, E, dense override, remapped ranks).
-struct PlanCacheEntry {
-  int64_t N = 0, HW = 0, E = 0;
-  bool dense = false;
-  int tail_min = 0;  // dense_tail_min() the plan was built with
-  std::vector<int32_t> ri, rj;
-  PlanMeta meta;
-};
-std::mutex g_cache_mu;
-// M3S_PLAN_CACHE=0: every solve call runs the host symbolic analysis (cold
-// calls; bench.py times them this way beside the cached figure)
-inline bool plan_cache_enabled() { return knobs().plan_cache != 0; }
-std::vector<PlanCacheEntry> g_cache;  // most recent first
-constexpr size_t kPlanCacheSize = 4;
-
 void set_lds_attributes_once() {
   static std::once_flag once;
   std::call_once(once, [] {
@@ -5580,425 +6071,6 @@ void set_lds_attributes_once() {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gn_prologue_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes);
   });
-}
-
-// Symbolic plan + LDS budget + full-range task table for remapped ranks.
-PlanMeta build_plan_meta(const m3s_gn_args *a, const Layout &Ly, const std::vector<int32_t> &ri,
-                         const std::vector<int32_t> &rj, bool force_dense) {
-  PlanMeta meta;
-  const int64_t E = a->E;
-  if (a->N > 1) {
-    SparsePlan P;
-    // The dispatch schedule (witems) and the split update lists (PART items)
-    // serve only the one-workgroup sparse_llt_kernel; a factor in global
-    // memory on the chip-wide path (df_factor / tail / column back-
-    // substitution) needs neither: at 256 KFs that halves the host analysis.
-    build_sparse_plan((int)a->N, ri, rj, P, 0, 0, dense_tail_min(), false);
-    const bool global_factor = sizeof(double) * ((size_t)(P.S + P.m) * 49 + (size_t)P.m * 7) > kMaxLdsBytes;
-    const bool chip_path = global_factor && cols_path() && P.m <= 512 && (P.nc == 0 || 7 * P.nc + 1 <= 16 * kTailMaxT);
-    if (global_factor && !chip_path)  // split long update lists for the staged global-factor products
-      build_sparse_plan((int)a->N, ri, rj, P, kSplitUpdates, Ly.slot_cap - 1, dense_tail_min(), true);
-    else if (!chip_path)
-      schedule_plan_items(P);
-    PlanImage img;
-    flatten_plan(P, img);
-    // df_factor_kernel's dispatch list: the sparse columns in level order,
-    // DIAG(k) then the OFF tasks of column k, then the dense-tail border tasks
-    meta.off_dfitems = (int)img.data.size();
-    for (int32_t k : P.corder) {
-      img.data.push_back(-1 - k);
-      for (int q = 0; q < P.col_ptr[k + 1] - P.col_ptr[k]; q++) img.data.push_back(P.ctask0[k] + q);
-    }
-    meta.n_dfsparse = (int)img.data.size() - meta.off_dfitems;
-    for (int b = 0; b < P.nc * (P.nc + 1) / 2; b++) img.data.push_back((int32_t)P.task_dst.size() + b);
-    meta.n_dfitems = (int)img.data.size() - meta.off_dfitems;
-    const bool fits = (int64_t)img.data.size() <= Ly.plan_cap && P.S <= Ly.slot_cap;
-    if (fits && !force_dense) {
-      meta.sparse = true;
-      meta.m = P.m;
-      meta.S = P.S;
-      meta.levels = P.levels;
-      meta.plan_len = (int)img.data.size();
-      meta.n_items = (int)P.items.size();
-      meta.n_tasks = (int)P.task_dst.size();
-      meta.n_parts = (int)P.part_q0.size();
-      meta.nc = P.nc;
-      meta.nnz = P.col_ptr.empty() ? 0 : P.col_ptr[P.m];
-      // LDS plan of sparse_llt_kernel<STORE>: flags always, factor + W + y if
-      // they fit, the plan too if it fits as well; else global factor with
-      // per-wave stage areas
-      const size_t flags_bytes =
-          sizeof(int32_t) * (((size_t)(P.S + 2 * P.m + P.part_q0.size()) + 1) & ~size_t(1));
-      const size_t fac_bytes = sizeof(double) * ((size_t)(P.S + P.m) * 49 + (size_t)P.m * 7);
-      const size_t plan_bytes = sizeof(int32_t) * ((img.data.size() + 1) & ~size_t(1));
-      const size_t stage_bytes = sizeof(double) * 16 * (size_t)kStageDoubles;
-      const size_t fin_bytes = sizeof(double) * kFin * (size_t)E;
-      if (fac_bytes + plan_bytes + flags_bytes <= kMaxLdsBytes) {
-        meta.store = 1;
-        meta.lds_bytes = fac_bytes + plan_bytes + flags_bytes;
-      } else if (fac_bytes + flags_bytes <= kMaxLdsBytes) {
-        meta.store = 2;
-        meta.lds_bytes = fac_bytes + flags_bytes;
-      }
-      if (meta.store != 0 && meta.lds_bytes + fin_bytes <= kMaxLdsBytes) {
-        meta.asm_lds = true;
-        meta.lds_bytes += fin_bytes;
-      }
-      if (meta.store == 0) {
-        meta.store = 0;
-        meta.lds_bytes = sizeof(double) * (size_t)P.m * 7 + flags_bytes + stage_bytes;
-        if (meta.lds_bytes > kMaxLdsBytes) meta.sparse = false;  // dense fallback
-      }
-      meta.h_plan = std::move(img.data);
-      img.data.clear();
-      meta.img = img;
-    }
-  }
-  (void)E;
-  return meta;
-}
-
-// Per solve call: read ii/jj (+ K) once — the call's only host sync — rank
-// the ids, fetch the plan (or defer it to the first solve) and enqueue ONE
-// upload of everything the launches read (pinned staging, above).
-
-// The per-call flag state the solve kernels of a plan rely on: the column-
-// task / dataflow / dense-tail epoch flags live only on the global-factor
-// path (the LDS-resident factors keep theirs in LDS), and no tagged granule
-// of an earlier call may match this call's epochs.
-bool reset_plan_flags(const PlanMeta &M, const Layout &Ly, void *ws, hipStream_t st) {
-  bool ok = true;
-  if (!(M.sparse && M.store != 0))
-    ok &= hipMemsetAsync(at<int32_t>(ws, Ly.colsync), 0, Ly.tail - Ly.colsync, st) == hipSuccess;
-  if (M.nc > 0)
-    ok &= hipMemsetAsync(at<double>(ws, Ly.tail) + tail_gran_offset_doubles(), 0,
-                         sizeof(double) * (tail_scratch_doubles() - tail_gran_offset_doubles()), st) == hipSuccess;
-  return ok;
-}
-
-// Upload a plan on the device's side stream and make `st` wait for it: the
-// copy runs while the first linearize kernel does instead of queueing behind
-// it. Callers have waited for every earlier launch on `st` (the prologue's
-// event or a stream sync), so nothing still running there reads `dst`.
-bool upload_plan(Staging *SG, PlanMeta &M, char *dst, hipStream_t st) {
-  if (!(M.sparse && !M.h_plan.empty())) return true;
-  const size_t nb = sizeof(int32_t) * M.h_plan.size();
-  if (SG->plan_pending && hipEventSynchronize(SG->plan_ev) != hipSuccess) return false;
-  SG->plan_pending = false;
-  if (!pinned_reserve(SG->plan_up, SG->plan_cap, nb)) return false;
-  memcpy(SG->plan_up, M.h_plan.data(), nb);
-  bool ok = hipMemcpyAsync(dst, SG->plan_up, nb, hipMemcpyHostToDevice, SG->side) == hipSuccess;
-  ok &= hipEventRecord(SG->plan_ev, SG->side) == hipSuccess;
-  ok &= hipStreamWaitEvent(st, SG->plan_ev, 0) == hipSuccess;
-  SG->plan_pending = ok;
-  return ok;
-}
-
-// Test hook for the bounded waits (tests/test_gpu_backend.py, knob
-// debug_drop_item): drop one item of sparse_llt_kernel's dispatch list, so the
-// items that read its blocks wait on a flag that is never set; the waits time
-// out and the iteration ends as a solve failure (dx = 0) instead of hanging.
-// On the chip-wide path (global factor) the item is dropped from
-// df_factor_kernel's dispatch list instead.
-void apply_drop_item(PlanMeta &M) {
-  const int d = drop_item_knob();
-  if (d < 0 || !M.sparse || M.h_plan.empty()) return;
-  if (M.store == 0 && M.n_dfitems > 0) {
-    int32_t *di = M.h_plan.data() + M.off_dfitems;
-    if (d < M.n_dfitems) {
-      for (int t = d; t + 1 < M.n_dfitems; t++) di[t] = di[t + 1];
-      M.n_dfitems -= 1;
-    }
-    return;
-  }
-  if (M.img.off_wave_ptr >= (int64_t)M.h_plan.size()) return;
-  int32_t *wp = M.h_plan.data() + M.img.off_wave_ptr, *wi = M.h_plan.data() + M.img.off_witems;
-  if (d < wp[1]) {
-    for (int t = d; t + 1 < wp[1]; t++) wi[t] = wi[t + 1];
-    wp[1] -= 1;
-  }
-}
-
-int gn_prepare_impl(const m3s_gn_args *a, hipStream_t st) {
-  const Layout Ly = gn_layout(a->N, a->HW, a->E);
-  void *ws = a->workspace;
-  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
-  Staging *SG = stage_for_device();
-  if (!SG) return M3S_ELAUNCH;
-  if (SG->pending && hipEventSynchronize(SG->ev) != hipSuccess) return M3S_ELAUNCH;
-  SG->pending = false;
-  const int64_t E = a->E;
-  if (!pinned_reserve(SG->down, SG->down_cap, 64 + 2 * sizeof(int64_t) * (size_t)E)) return M3S_ELAUNCH;
-  float *hK = reinterpret_cast<float *>(SG->down);  // calib intrinsics, read with ii/jj
-  int64_t *hii = reinterpret_cast<int64_t *>(SG->down + 64), *hjj = hii + E;
-  for (int q = 0; q < 9; q++) hK[q] = 0.f;
-  if (a->mode == M3S_MODE_CALIB &&
-      hipMemcpyAsync(hK, a->K, sizeof(float) * 9, hipMemcpyDeviceToHost, st) != hipSuccess)
-    return M3S_ELAUNCH;
-  if (a->N > 1 && a->dx_out && hipMemsetAsync(a->dx_out, 0, sizeof(float) * 7 * (a->N - 1), st) != hipSuccess)
-    return M3S_ELAUNCH;
-  if (E > 0 && hipMemcpyAsync(hii, a->ii, sizeof(int64_t) * E, hipMemcpyDeviceToHost, st) != hipSuccess)
-    return M3S_ELAUNCH;
-  if (E > 0 && hipMemcpyAsync(hjj, a->jj, sizeof(int64_t) * E, hipMemcpyDeviceToHost, st) != hipSuccess)
-    return M3S_ELAUNCH;
-  if (hipStreamSynchronize(st) != hipSuccess) return M3S_ELAUNCH;
-  std::vector<int32_t> ri, rj;
-  const int nu = host_remap(hii, hjj, E, ri, rj);
-  const bool bad = nu > a->N;
-  const bool force_dense = force_dense_knob();
-  PlanMeta meta;
-  bool hit = false;
-  if (!bad && plan_cache_enabled()) {
-    std::lock_guard<std::mutex> g(g_cache_mu);
-    for (size_t q = 0; q < g_cache.size(); q++) {
-      const PlanCacheEntry &C = g_cache[q];
-      if (C.N == a->N && C.HW == a->HW && C.E == E && C.dense == force_dense &&
-          C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
-        meta = C.meta;
-        std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
-        hit = true;
-        break;
-      }
-    }
-  }
-  if (hit && E > 0 && meta.eorder.empty()) build_eorder(meta.rj, 0, E, meta.eorder);  // cached by the prologue path
-  if (!hit) {
-    // ranks and the full-range task table now (the first linearize needs
-    // them); the symbolic plan is built by the first solve of this call,
-    // while the first linearize kernel runs (finish_plan)
-    meta.h_ri = ri;
-    meta.rj = rj;
-    if (E > 0) build_eorder(meta.rj, 0, E, meta.eorder);
-    meta.sparse = !bad && !force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
-    meta.plan_pending = !bad && a->N > 1;
-    meta.force_dense = force_dense;
-  }
-  for (int q = 0; q < 8; q++) meta.h_info[q] = 0;
-  for (int q = 0; q < 64; q++) meta.h_flags[q] = 0;
-  meta.h_info[M3S_INFO_N_UNIQUE] = nu;
-  if (bad) meta.h_info[M3S_INFO_BAD_EDGE] = 1, meta.h_flags[kFlagStop] = 1;
-  if (a->mode == M3S_MODE_CALIB) {  // K row-major: fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]
-    meta.has_K = true;
-    meta.K4[0] = hK[0], meta.K4[1] = hK[4], meta.K4[2] = hK[2], meta.K4[3] = hK[5];
-  }
-  meta.planes_ok = false;
-  meta.range_b = 0, meta.range_e = E, meta.order_ok = E > 0;
-  if (meta.sparse && !meta.plan_pending && meta.lds_bytes > 64 * 1024) set_lds_attributes_once();
-  std::lock_guard<std::mutex> g(g_reg_mu);
-  PlanMeta &M = g_reg[ws];
-  M = std::move(meta);
-  bool ok = true;
-  if (!M.plan_pending) ok &= reset_plan_flags(M, Ly, ws, st);
-  M.epoch = 0;
-  if (!M.plan_pending) apply_drop_item(M);
-  // one upload: flags | rank_i | rank_j | edge counters | edge order [| plan] (the
-  // layout keeps them in this order), then info (the caller's tensor) from
-  // the same buffer
-  const bool with_plan = M.sparse && !M.plan_pending && !M.h_plan.empty();
-  const bool with_tasks = E > 0;
-  size_t n_up = with_plan ? Ly.plan - Ly.flags + sizeof(int32_t) * M.h_plan.size()
-                          : with_tasks ? Ly.eorder - Ly.flags + sizeof(int32_t) * M.eorder.size()
-                                       : Ly.edge_cnt - Ly.flags + edge_cnt_bytes(E);
-  n_up = align_up(n_up, 16);
-  if (!pinned_reserve(SG->up, SG->up_cap, n_up + sizeof M.h_info)) return M3S_ELAUNCH;
-  char *up = SG->up;
-  memcpy(up, M.h_flags, sizeof M.h_flags);
-  memset(up + (Ly.edge_cnt - Ly.flags), 0, edge_cnt_bytes(E));  // the fused finalize's counters
-  if (E > 0) {
-    memcpy(up + (Ly.rank_i - Ly.flags), M.h_ri.data(), sizeof(int32_t) * E);
-    memcpy(up + (Ly.rank_j - Ly.flags), M.rj.data(), sizeof(int32_t) * E);
-  }
-  if (with_tasks) memcpy(up + (Ly.eorder - Ly.flags), M.eorder.data(), sizeof(int32_t) * M.eorder.size());
-  if (with_plan) memcpy(up + (Ly.plan - Ly.flags), M.h_plan.data(), sizeof(int32_t) * M.h_plan.size());
-  memcpy(up + n_up, M.h_info, sizeof M.h_info);
-  ok &= hipMemcpyAsync(at<char>(ws, Ly.flags), up, n_up, hipMemcpyHostToDevice, st) == hipSuccess;
-  ok &= hipMemcpyAsync(a->info, up + n_up, sizeof M.h_info, hipMemcpyHostToDevice, st) == hipSuccess;
-  ok &= hipEventRecord(SG->ev, st) == hipSuccess;
-  SG->pending = ok;
-  return ok ? M3S_OK : M3S_ELAUNCH;
-}
-
-// The deferred half of a cold prepare: the symbolic plan (ordering, fill,
-// update lists; build_plan_meta) on the host, its upload, and the per-plan
-// flag resets. Called by a call's first solve, i.e. after its first
-// linearize is on the stream: the analysis runs while that kernel does.
-int finish_plan(const m3s_gn_args *a, const Layout &Ly, hipStream_t st) {
-  void *ws = a->workspace;
-  std::vector<int32_t> ri, rj;
-  bool force_dense;
-  {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    auto it = g_reg.find(ws);
-    if (it == g_reg.end()) return M3S_EINVAL;
-    if (!it->second.plan_pending) return M3S_OK;
-    ri = it->second.h_ri;
-    rj = it->second.rj;
-    force_dense = it->second.force_dense;
-  }
-  PlanMeta built = build_plan_meta(a, Ly, ri, rj, force_dense);
-  if (built.sparse && built.lds_bytes > 64 * 1024) set_lds_attributes_once();
-  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
-  Staging *SG = stage_for_device();
-  if (!SG) return M3S_ELAUNCH;
-  if (SG->plan_pending && hipEventSynchronize(SG->plan_ev) != hipSuccess) return M3S_ELAUNCH;
-  SG->plan_pending = false;
-  std::lock_guard<std::mutex> g(g_reg_mu);
-  PlanMeta &M = g_reg[ws];
-  M.sparse = built.sparse, M.store = built.store, M.asm_lds = built.asm_lds, M.lds_bytes = built.lds_bytes;
-  M.m = built.m, M.S = built.S, M.levels = built.levels, M.plan_len = built.plan_len;
-  M.n_items = built.n_items, M.n_tasks = built.n_tasks, M.n_parts = built.n_parts, M.nc = built.nc;
-  M.off_dfitems = built.off_dfitems, M.n_dfitems = built.n_dfitems, M.nnz = built.nnz;
-  M.n_dfsparse = built.n_dfsparse;
-  M.img = built.img;
-  M.h_plan = std::move(built.h_plan);
-  M.plan_pending = false;
-  if (plan_cache_enabled()) {
-    PlanCacheEntry C;
-    C.N = a->N, C.HW = a->HW, C.E = a->E, C.dense = force_dense, C.ri = ri, C.rj = rj;
-    C.tail_min = dense_tail_min();
-    C.meta = M;
-    std::lock_guard<std::mutex> gc(g_cache_mu);
-    g_cache.insert(g_cache.begin(), std::move(C));
-    if (g_cache.size() > kPlanCacheSize) g_cache.pop_back();
-  }
-  bool ok = reset_plan_flags(M, Ly, ws, st);
-  apply_drop_item(M);
-  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
-  return ok ? M3S_OK : M3S_ELAUNCH;
-}
-
-// The host half of an async prepare (gn_prepare_async), at the first point a
-// call needs its ids on the host (its first solve, or a sharded rank's edge
-// range): wait for the prologue (normally long done: the first linearize is
-// queued behind it), read ii / jj / K from the pinned slot, rank the ids on
-// the host (the plan and its cache key need them), and fetch the cached plan;
-// a miss leaves the plan to finish_plan. The linearize state of the entry
-// (range, task table, planes) is the prologue's and stays.
-int host_finish(const m3s_gn_args *a, hipStream_t st) {
-  void *ws = a->workspace;
-  int slot = -1;
-  {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    auto it = g_reg.find(ws);
-    if (it == g_reg.end()) return M3S_EINVAL;
-    if (!it->second.host_pending) return M3S_OK;
-    slot = it->second.slot;
-  }
-  const int64_t E = a->E;
-  std::vector<int64_t> hii((size_t)E), hjj((size_t)E);
-  float hK[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  {
-    std::lock_guard<std::mutex> stage_lock(g_stage_mu);
-    Staging *SG = stage_for_device();
-    if (!SG || slot < 0 || slot >= (int)SG->slots.size()) return M3S_ELAUNCH;
-    DownSlot &D = SG->slots[slot];
-    if (hipEventSynchronize(D.ev) != hipSuccess) return M3S_ELAUNCH;
-    if (a->mode == M3S_MODE_CALIB) memcpy(hK, D.p, sizeof hK);
-    if (E > 0) {
-      memcpy(hii.data(), D.p + 64, sizeof(int64_t) * (size_t)E);
-      memcpy(hjj.data(), D.p + 64 + sizeof(int64_t) * (size_t)E, sizeof(int64_t) * (size_t)E);
-    }
-    D.busy = false;
-  }
-  std::vector<int32_t> ri, rj;
-  const int nu = host_remap(hii.data(), hjj.data(), E, ri, rj);
-  const bool bad = nu > a->N;  // the prologue has stopped the call (flags, info)
-  const Layout Ly = gn_layout(a->N, a->HW, a->E);
-  bool force_dense;
-  {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    force_dense = g_reg.at(ws).force_dense;
-  }
-  PlanMeta hitm;
-  bool hit = false;
-  if (!bad && plan_cache_enabled()) {
-    std::lock_guard<std::mutex> g(g_cache_mu);
-    for (size_t q = 0; q < g_cache.size(); q++) {
-      const PlanCacheEntry &C = g_cache[q];
-      if (C.N == a->N && C.HW == a->HW && C.E == E && C.dense == force_dense &&
-          C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
-        hitm = C.meta;
-        std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
-        hit = true;
-        break;
-      }
-    }
-  }
-  if (hit && hitm.sparse && hitm.lds_bytes > 64 * 1024) set_lds_attributes_once();
-  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
-  Staging *SG = stage_for_device();
-  if (!SG) return M3S_ELAUNCH;
-  std::lock_guard<std::mutex> g(g_reg_mu);
-  PlanMeta &M = g_reg[ws];
-  M.host_pending = false, M.slot = -1;
-  M.h_ri = std::move(ri), M.rj = std::move(rj);
-  M.K4[0] = hK[0], M.K4[1] = hK[4], M.K4[2] = hK[2], M.K4[3] = hK[5];
-  if (bad) {
-    M.sparse = false, M.plan_pending = false;
-    return M3S_OK;
-  }
-  if (!hit) return M3S_OK;  // plan_pending: finish_plan builds it
-  M.sparse = hitm.sparse, M.store = hitm.store, M.asm_lds = hitm.asm_lds, M.lds_bytes = hitm.lds_bytes;
-  M.m = hitm.m, M.S = hitm.S, M.levels = hitm.levels, M.plan_len = hitm.plan_len;
-  M.n_items = hitm.n_items, M.n_tasks = hitm.n_tasks, M.n_parts = hitm.n_parts, M.nc = hitm.nc;
-  M.off_dfitems = hitm.off_dfitems, M.n_dfitems = hitm.n_dfitems, M.nnz = hitm.nnz;
-  M.n_dfsparse = hitm.n_dfsparse;
-  M.img = hitm.img;
-  M.h_plan = std::move(hitm.h_plan);
-  M.plan_pending = false;
-  bool ok = reset_plan_flags(M, Ly, ws, st);
-  apply_drop_item(M);
-  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
-  return ok ? M3S_OK : M3S_ELAUNCH;
-}
-
-// Prepare a call without a host round trip: one prologue kernel on the stream
-// (ranks, task table, flags, info, dx_out; the ids to pinned memory) and the
-// registry entry; the host reads the ids later (host_finish), while the first
-// linearize runs. Large edge sets (> kProMaxE) take the synchronous prepare.
-int gn_prepare_async(const m3s_gn_args *a, hipStream_t st) {
-  const int64_t E = a->E;
-  if (E > kProMaxE || a->N > (int64_t)1 << 30 || knobs().prologue == 0) return gn_prepare_impl(a, st);
-  const Layout Ly = gn_layout(a->N, a->HW, E);
-  void *ws = a->workspace;
-  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
-  Staging *SG = stage_for_device();
-  if (!SG) return M3S_ELAUNCH;
-  const int slot = acquire_slot(*SG, 64 + 2 * sizeof(int64_t) * (size_t)E);
-  if (slot < 0) return M3S_ELAUNCH;
-  DownSlot &D = SG->slots[slot];
-  ProArgs P;
-  P.ii = a->ii, P.jj = a->jj;
-  P.K = a->mode == M3S_MODE_CALIB ? a->K : nullptr;
-  P.down_K = reinterpret_cast<float *>(D.dp);
-  P.down_ii = reinterpret_cast<int64_t *>(D.dp + 64);
-  P.down_jj = P.down_ii + E;
-  P.E = (int)E, P.N = (int)a->N, P.P2 = prologue_p2(E);
-  P.flags = at<int32_t>(ws, Ly.flags), P.rank_i = at<int32_t>(ws, Ly.rank_i), P.rank_j = at<int32_t>(ws, Ly.rank_j);
-  P.eorder = at<int32_t>(ws, Ly.eorder), P.info = a->info, P.edge_cnt = at<uint32_t>(ws, Ly.edge_cnt);
-  P.dx_out = a->dx_out;
-  P.n_dx = (a->N > 1 && a->dx_out) ? (int)(7 * (a->N - 1)) : 0;
-  const size_t lds = prologue_lds(P.E, P.P2);
-  if (lds > 64 * 1024) set_lds_attributes_once();
-  gn_prologue_kernel<<<1, kProThreads, lds, st>>>(P);
-  if (launch_ok() != M3S_OK || hipEventRecord(D.ev, st) != hipSuccess) {
-    D.busy = false;
-    return M3S_ELAUNCH;
-  }
-  PlanMeta meta;
-  meta.host_pending = true, meta.slot = slot;
-  meta.has_K = a->mode == M3S_MODE_CALIB;
-  meta.force_dense = force_dense_knob();
-  meta.sparse = !meta.force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
-  meta.plan_pending = a->N > 1;
-  meta.range_b = 0, meta.range_e = E, meta.order_ok = E > 0;
-  std::lock_guard<std::mutex> g(g_reg_mu);
-  PlanMeta &M = g_reg[ws];
-  if (M.host_pending && M.slot >= 0 && M.slot < (int)SG->slots.size() && M.slot != slot)
-    SG->slots[M.slot].busy = false;  // a re-prepare of a workspace whose ids were never read
-  M = std::move(meta);
-  M.epoch = 0;
-  return M3S_OK;
 }
 
 // In-call launch timing (bench.py's roofline leg, m3s_debug_call_timing):
@@ -6098,728 +6170,12 @@ int gn_full(const m3s_gn_args *a, int mode, void *stream) {
   return M3S_OK;
 }
 
-// --------------------------------------------------------------- tracker --
+}  // namespace
 
-constexpr size_t kTrackStateOff = 0;
+#include "gn/track.h"
+#include "gn/track_frame.h"
 
-struct TrackSync;
-// Zeroes the sync words and the persistent kernel's partial granules (n_part
-// 16-B granules, 0 on the launch-per-iteration path) of THIS call: a granule
-// is accepted once its tag equals it + 1, so a granule left with tag 1 by a
-// call that stopped after its first iteration (or a reused allocation holding
-// such a word) must never be read as iteration 0's partial.
-__global__ void __launch_bounds__(256) track_init_kernel(const float *T_WCf, const float *T_WCk, TrackState *st,
-                                                         int32_t *info, float *T_WCf_out, float *T_CkCf_out,
-                                                         uint32_t *sync_words, int n_sync, u32x4 *part, int n_part) {
-  for (int k = threadIdx.x; k < n_sync; k += blockDim.x) sync_words[k] = 0u;
-  for (int k = threadIdx.x; k < n_part; k += blockDim.x) part[k] = u32x4{0u, 0u, 0u, 0u};
-  if (threadIdx.x != 0) return;
-  const Sim3f Tk = load_sim3(T_WCk), Tf = load_sim3(T_WCf);
-  const Sim3f R = compose(inverse(Tk), Tf);
-  store_sim3(st->T_rel, R);
-  store_sim3(st->T_WCk, Tk);
-  st->old_cost = __builtin_inf();
-  st->done = 0;
-  st->arrive = 0;
-  for (int k = 0; k < 8; k++) info[k] = 0;
-  store_sim3(T_CkCf_out, R);
-  store_sim3(T_WCf_out, Tf);
-}
-
-// One tracker GN update from the reduced sums s (kL / kG / kCost layout):
-// 7x7 fp64 Cholesky of H (one thread, fully unrolled; 1/L_kk by rsqrt_nr:
-// v_rsq_f64 + one Newton step, 4.2e-15 relative, round 4 -- the tracker's
-// fixture parity, 1e-5 + 1e-4 sum|tau| per pose, holds with it; no IEEE sqrt /
-// division sequences on the serial chain),
-// tau = -H^-1 g (tracker.py:156-171: g = sum w e J with e = pred - meas), the
-// retraction T <- Exp(tau) T, and check_convergence (nonlinear_optimizer.py:
-// 5-25; rel is NaN on the first step, old_cost = inf). T and old_cost are
-// updated in place unless the Cholesky fails.
-constexpr int kTrackContinue = 0, kTrackConverged = 1, kTrackFailed = 2;
-// A/B: the tracker's 7x7 Cholesky solve in fp32 (the reference's precision,
-// tracker.py:168) instead of fp64: +1% GN it/s at C2
-// (profiles/r05/trk_ab_f32_solve_REJECTED.txt), not worth the precision
-__device__ __forceinline__ int track_update(const double *s, Sim3f &T, double &old_cost, float rel_error,
-                                            float delta_norm) {
-  typedef double real;
-  real H[7][7], L[7][7], g[7], y[7], x[7];
-  for (int a = 0; a < 7; a++)
-    for (int c = 0; c < 7; c++) H[a][c] = (real)s[kL + tri(a < c ? a : c, a < c ? c : a)];
-  for (int a = 0; a < 7; a++) g[a] = (real)s[kG + a];
-  const double cost = 0.5 * s[kCost];
-  real dinv[7];
-#pragma unroll
-  for (int a = 0; a < 7; a++)
-#pragma unroll
-    for (int c = 0; c < 7; c++) L[a][c] = 0.0;
-#pragma unroll
-  for (int k = 0; k < 7; k++) {
-    real d = H[k][k];
-#pragma unroll
-    for (int p = 0; p < k; p++) d -= L[k][p] * L[k][p];
-    if (!(d > (real)0)) return kTrackFailed;
-    dinv[k] = rsqrt_nr(d);
-    L[k][k] = d * dinv[k];
-#pragma unroll
-    for (int i = k + 1; i < 7; i++) {
-      real v = H[i][k];
-#pragma unroll
-      for (int p = 0; p < k; p++) v -= L[i][p] * L[k][p];
-      L[i][k] = v * dinv[k];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 7; i++) {
-    real v = -g[i];
-#pragma unroll
-    for (int p = 0; p < i; p++) v -= L[i][p] * y[p];
-    y[i] = v * dinv[i];
-  }
-#pragma unroll
-  for (int i = 6; i >= 0; i--) {
-    real v = y[i];
-#pragma unroll
-    for (int p = i + 1; p < 7; p++) v -= L[p][i] * x[p];
-    x[i] = v * dinv[i];
-  }
-  float tau[7];
-  float n2 = 0.0f;
-  for (int k = 0; k < 7; k++) {
-    tau[k] = (float)x[k];
-    n2 += tau[k] * tau[k];
-  }
-  T = retract(tau, T);
-  const float cost_f = (float)cost;  // the reference's cost is a python float of an fp32 .item()
-  const double rel = fabs((old_cost - (double)cost_f) / old_cost);  // NaN on the first step
-  old_cost = (double)cost_f;
-  return (rel < (double)rel_error || sqrtf(n2) < delta_norm) ? kTrackConverged : kTrackContinue;
-}
-
-// reduce chunk partials, 7x7 fp64 Cholesky, tau = -H^-1 g, retraction,
-// convergence (nonlinear_optimizer.py:5-25), outputs.
-constexpr int kTrackSolveThreads = 256;  // = the linearize block (the fused solve runs in one)
-__device__ void track_solve_block(const LinArgs &A) {
-  const float *__restrict__ partials = A.partials;
-  const int64_t chunks = A.chunks;
-  TrackState *st = A.track;
-  int32_t *info = A.info;
-  const float rel_error = A.rel_error, delta_norm = A.delta_norm;
-  float *T_WCf_out = A.T_WCf_out, *T_CkCf_out = A.T_CkCf_out;
-  // fp64 sums of the chunk partials: thread t adds chunks t, t + 256, ... (all
-  // 36 values of a chunk are loaded together), then a fixed tree over the
-  // threads (wave butterfly, then the 4 waves in order): deterministic, and
-  // every load is in flight at once instead of one dependent chain per value
-  __shared__ double s[kNP], wpart[kTrackSolveThreads / 64][kNP];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  double acc[kNP];
-#pragma unroll
-  for (int k = 0; k < kNP; k++) acc[k] = 0.0;
-  for (int64_t c = t; c < chunks; c += kTrackSolveThreads) {
-    const float4 *p4 = reinterpret_cast<const float4 *>(partials + (size_t)c * kNP);
-#pragma unroll
-    for (int q = 0; q < kNP / 4; q++) {
-      const float4 v = p4[q];
-      acc[4 * q] += (double)v.x, acc[4 * q + 1] += (double)v.y;
-      acc[4 * q + 2] += (double)v.z, acc[4 * q + 3] += (double)v.w;
-    }
-  }
-  int xi;
-  bool xv;
-  const double xs = xreduce36(acc, lane, xi, xv);  // transposed wave reduction (store_partial)
-  if (xv) wpart[wv][xi] = xs;
-  __syncthreads();
-  if (t < kNP) {
-    double a = 0.0;
-#pragma unroll
-    for (int w = 0; w < kTrackSolveThreads / 64; w++) a += wpart[w][t];
-    s[t] = a;
-  }
-  __syncthreads();
-  if (t != 0) return;
-  Sim3f T = load_sim3(st->T_rel);
-  double old = st->old_cost;
-  const int r = track_update(s, T, old, rel_error, delta_norm);
-  info[M3S_INFO_ITERS] += 1;
-  if (r == kTrackFailed) {  // torch.linalg.cholesky raises -> tracking failure
-    info[M3S_INFO_SOLVE_FAIL] = 1;
-    st->done = 1;
-    return;
-  }
-  store_sim3(st->T_rel, T);
-  store_sim3(T_CkCf_out, T);
-  store_sim3(T_WCf_out, compose(load_sim3(st->T_WCk), T));
-  if (r == kTrackConverged) {
-    st->done = 1;
-    info[M3S_INFO_CONVERGED] = 1;
-  }
-  st->old_cost = old;
-}
-
-// ------------------------------------------------ persistent tracker GN --
-// All iterations of one frame -> keyframe solve in ONE launch (tracker.py:
-// 173-266). G <= 256 workgroups, one per CU, each owning PPL pixels per lane.
-// A lane loads its pixels' inputs once (target-side PixIn from Xk / Q / valid
-// and the source point Xf) and keeps them in registers across iterations, so
-// iterations 2.. read nothing from HBM. Per iteration (round 4: every
-// hand-off is a tagged 16-B granule, {payload | it + 1}, stored write-through
-// and polled by its reader; a 16-B store lands whole, so no drain, counter or
-// second load of the payload sits on the critical path):
-//   1. each workgroup accumulates its pixels (the packed Accum of the backend
-//      kernels) and stores its 36-float partial as 12 granules;
-//   2. workgroup s < 8 polls the granules of shard s = {s, s + 8, ...} (lane j:
-//      member s + 8 j), sums them across lanes in a fixed order (fp64) and
-//      publishes the 36 shard sums as granules;
-//   3. workgroup 0 polls the 8 shards' granules, sums them in shard order,
-//      runs the 7x7 update (track_update) and publishes the record (pose,
-//      status, cost) as 4 granules; every other workgroup polls those.
-// Reuse of the granules is safe: a workgroup stores iteration it + 1's
-// partial only after it read iteration it's record, which workgroup 0
-// published after every shard reducer had read iteration it's partials.
-// The reduction order is fixed (deterministic). Waits are bounded: a timed-out
-// shard sum is NaN (the update then fails, info[SOLVE_FAIL] = 1), a timed-out
-// record poll ends the solve with info[SOLVE_FAIL] = 2. Round 2 and 3 used
-// drained sc1 stores + agent atomic counters (MI355X_MICROARCH.md
-// inter-workgroup table, row 1): 95-99k GN it/s at C2 against ~112k+ now.
-// workgroup size: 256 threads (one wave per SIMD: the block reduction's waves
-// do not take turns; 116-121k -> 124-125k GN it/s at C2, round 4) while the
-// image fits 4 pixels per lane, else 512
-constexpr int kTrkThreadsLo = 256, kTrkThreadsHi = 512;
-constexpr int kTrkMaxBlocks = 256;
-constexpr int kTrkShards = 8;
-constexpr int kTrkGran = kNP / 3;  // 16-B granules per workgroup partial (3 sums + tag)
-constexpr int kTrkSpins = 1 << 22;
-// The per-iteration accumulation runs on pixel pairs (AccumPP /
-// pixel_contrib2, as the backend's packed kernel; round 5). Measured and
-// removed (DESIGN.md §4 Tracker): every workgroup running the top level
-// itself, and no shard level.
-constexpr int kTrkShBufs = 1;
-struct TrackSync {
-  uint32_t rec[32];  // the published record: 4 tagged 16-B granules (pose 0-7, status 8, cost 9-10 | tag)
-  uint32_t shard_sum[kTrkShBufs][kTrkShards][kNP][4];  // level-1 sums (fp64), tagged 16-B granules {lo, hi, tag, 0}
-};
-static_assert(offsetof(TrackSync, rec) % 128 == 0, "the record granules share one line");
-inline size_t track_sync_off() { return 128; }  // after TrackState (<= 128 B)
-inline size_t track_part_off() { return track_sync_off() + sizeof(TrackSync); }
-static_assert(sizeof(TrackState) <= 128, "TrackState must fit before the sync lines");
-static_assert((128 + sizeof(TrackSync)) % 16 == 0, "the partial granules are 16-B aligned");
-
-#ifdef M3S_TRK_STAMPS  // phase stamps of workgroups 0 and G - 1 (tools/trk_stamps.py)
-__device__ int64_t g_trk_stamp[2][16][8];
-#define M3S_TSTAMP(ph)                                                                     \
-  if (t == 0 && (b == 0 || b == G - 1) && it < 16) g_trk_stamp[b == 0 ? 0 : 1][it][ph] = wall_clock64();
-#else
-#define M3S_TSTAMP(ph)
-#endif
-// M3S_TRK_SLEEP: s_sleep(1) per failed poll pass (0: spin; correct either
-// way, the poll loads are poll_b128)
-#ifndef M3S_TRK_SLEEP
-#define M3S_TRK_SLEEP 1
-#endif
-__device__ __forceinline__ void trk_pause() {
-#if M3S_TRK_SLEEP
-  __builtin_amdgcn_s_sleep(1);
-#endif
-}
-template <int MODE, int PPL, int TH>
-__global__ void __launch_bounds__(TH) track_persistent_kernel(LinArgs A, int max_iters, TrackSync *sync) {
-  const int G = (int)gridDim.x, b = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, wv = t >> 6;
-  constexpr int NW = TH / 64;
-  __shared__ float redf[NW][kNP];
-  __shared__ double s_sum[kNP];
-  // the iteration's record: pose (0-7), status (8: kTrackContinue /
-  // kTrackConverged / kTrackFailed / 3 = barrier timeout), cost (9-10)
-  __shared__ uint32_t pub_s[12];
-  __shared__ __attribute__((aligned(16))) float blk_s[kNP];
-  TrackState *st = A.track;
-  const int64_t HW = A.HW;
-  PixIn<MODE> in[PPL];
-  float Xf[PPL][3];
-  bool live[PPL];
-#pragma unroll
-  for (int s = 0; s < PPL; s++) {
-    const int64_t p = ((int64_t)b * PPL + s) * TH + t;
-    live[s] = p < HW;
-    const int64_t pc = live[s] ? p : 0;
-    in[s] = gather_pixel<MODE, true>(A, A.Xs, nullptr, pc, A.valid[pc] != 0, 0, A.Q[pc], 0.0f);
-    Xf[s][0] = A.Xsrc[3 * pc], Xf[s][1] = A.Xsrc[3 * pc + 1], Xf[s][2] = A.Xsrc[3 * pc + 2];
-  }
-  Sim3f T = load_sim3(st->T_rel);
-  const Sim3f Tk = load_sim3(st->T_WCk);
-  int it = 0, status = kTrackContinue;
-  // the record granules (lanes >= 4: offsets past the range, loads read zeros
-  // and stores are dropped)
-  const __amdgpu_buffer_rsrc_t Rrec = __builtin_amdgcn_make_buffer_rsrc(sync->rec, 0, 64, 0x00020000);
-  const __amdgpu_buffer_rsrc_t Rsh = __builtin_amdgcn_make_buffer_rsrc(sync->shard_sum, 0, (int)sizeof(sync->shard_sum), 0x00020000);
-  constexpr int kShFar = (int)sizeof(TrackSync::shard_sum);  // past the range: no access
-  const __amdgpu_buffer_rsrc_t Rpart =
-      __builtin_amdgcn_make_buffer_rsrc(A.partials, 0, kTrkMaxBlocks * kTrkGran * 16, 0x00020000);
-  constexpr int kPartFar = kTrkMaxBlocks * kTrkGran * 16;
-  for (; it < max_iters; it++) {
-    M3S_TSTAMP(0)
-    const Sim3Mat Tm = sim3_matrix(T);
-    float v[kNP];
-#pragma unroll
-    for (int k = 0; k < kNP; k++) v[k] = 0.0f;
-    {  // pixel pairs in the halves of float2 registers (the backend's packed
-       // accumulation, with the cost sum); a lane's pixel past the image takes
-       // a zero weight
-      constexpr int NPL = PixIn<MODE>::kPlanes, SQK = MODE == 2 ? 1 : NPL - 1;
-      AccumPP acc;
-      acc.zero();
-#pragma unroll
-      for (int s = 0; s < PPL; s += 2) {
-        const int s1 = s + 1 < PPL ? s + 1 : s;
-        f32x2 in2[NPL], X2[3], Y2[3];
-#pragma unroll
-        for (int k = 0; k < NPL; k++) {
-          const float lo = (k == SQK && !live[s]) ? 0.0f : in[s].v[k];
-          const float hi = (k == SQK && (!live[s1] || s1 == s)) ? 0.0f : in[s1].v[k];
-          in2[k] = f32x2{lo, hi};
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) X2[k] = f32x2{Xf[s][k], Xf[s1][k]};
-        act2(Tm, X2, Y2);
-        pixel_contrib2<MODE, NPL, true>(acc, A.P, in2, Y2);
-      }
-      acc.fold(v);
-    }
-    M3S_TSTAMP(1)
-    {
-      int idx;
-      bool ok;
-      const float x = xreduce36_trk(v, lane, idx, ok);
-      if (ok) redf[wv][idx] = x;
-    }
-    __syncthreads();
-    if (wv == 0) {
-      // block partial -> LDS -> 12 tagged 16-B granules {3 sums | it + 1}
-      // (write-through, no drain: the shard reducer polls them)
-      if (lane < kNP) {
-        float x = 0.0f;
-#pragma unroll
-        for (int w = 0; w < NW; w++) x += redf[w][lane];
-        blk_s[lane] = x;
-      }
-      wave_lds_fence();
-      {
-        const int q = lane < kTrkGran ? 3 * lane : 0;
-        const u32x4 w = {__float_as_uint(blk_s[q]), __float_as_uint(blk_s[q + 1]), __float_as_uint(blk_s[q + 2]),
-                         (unsigned)(it + 1)};
-        __builtin_amdgcn_raw_buffer_store_b128(w, Rpart, lane < kTrkGran ? (b * kTrkGran + lane) * 16 : kPartFar, 0, 16);
-      }
-      M3S_TSTAMP(2)
-      const int shb = 0;  // the shard-sum buffer
-      // level 1: workgroup s < 8 reduces shard s = {s, s + 8, ...}: lane j
-      // polls member s + 8 j's granules, then the 36 sums are reduced across
-      // the lanes in a fixed order (fp64)
-      const int sh = b;
-      const uint32_t n_top = (uint32_t)(G < kTrkShards ? G : kTrkShards);
-      bool top_last = false;
-      if (b < kTrkShards) {
-        const int n_sh = (G - sh + kTrkShards - 1) / kTrkShards;
-        u32x4 g[kTrkGran];
-        int spins = 0;
-        for (;;) {
-#pragma unroll
-          for (int k = 0; k < kTrkGran; k++)
-            g[k] = poll_b128(Rpart, lane < n_sh ? ((sh + kTrkShards * lane) * kTrkGran + k) * 16 : kPartFar);
-          bool ok = true;
-#pragma unroll
-          for (int k = 0; k < kTrkGran; k++) ok &= lane >= n_sh || g[k].w == (unsigned)(it + 1);
-          if (__ballot(!ok) == 0) break;
-          trk_pause();
-          if (++spins > kTrkSpins) break;
-        }
-        double a[kNP];
-#pragma unroll
-        for (int k = 0; k < kTrkGran; k++) {
-          a[3 * k] = (double)__uint_as_float(g[k].x);
-          a[3 * k + 1] = (double)__uint_as_float(g[k].y);
-          a[3 * k + 2] = (double)__uint_as_float(g[k].z);
-        }
-        // a timed-out shard publishes a NaN sum: the update fails (status 2)
-        if (spins > kTrkSpins) a[0] = __builtin_nan("");
-        int idx;
-        bool ok;
-        const double x = xreduce36_trk(a, lane, idx, ok);
-        {
-          const unsigned long long xb = (unsigned long long)__double_as_longlong(x);
-          const u32x4 w = {(unsigned)(xb & 0xffffffffull), (unsigned)(xb >> 32), (unsigned)(it + 1), 0u};
-          __builtin_amdgcn_raw_buffer_store_b128(w, Rsh, ok ? ((shb * kTrkShards + sh) * kNP + idx) * 16 : kShFar, 0, 16);
-        }
-        // level 2: workgroup 0 sums the shard sums in shard order as their
-        // granules land
-        top_last = sh == 0;
-      }
-      if (top_last) {
-        M3S_TSTAMP(3)
-        u32x4 g[kTrkShards];
-        int spins = 0;
-        for (;;) {
-#pragma unroll
-          for (int j = 0; j < kTrkShards; j++)
-            g[j] = poll_b128(Rsh, (lane < kNP && j < (int)n_top) ? (j * kNP + lane) * 16 : kShFar);
-          bool ok = true;
-#pragma unroll
-          for (int j = 0; j < kTrkShards; j++) ok &= lane >= kNP || j >= (int)n_top || g[j].z == (unsigned)(it + 1);
-          if (__ballot(!ok) == 0) break;
-          trk_pause();
-          if (++spins > kTrkSpins) break;
-        }
-        if (lane < kNP) {
-          double x = 0.0;
-#pragma unroll
-          for (int j = 0; j < kTrkShards; j++)
-            x += j < (int)n_top ? __longlong_as_double((long long)(((unsigned long long)g[j].y << 32) | g[j].x)) : 0.0;
-          s_sum[lane] = x;
-        }
-        const bool timed_out = spins > kTrkSpins;  // bounded wait: published as status 3
-        wave_lds_fence();
-        M3S_TSTAMP(4)
-        if (lane == 0) {
-          // the previous record's cost (inf first)
-          double oc = it == 0 ? __builtin_inf()
-                              : __longlong_as_double((long long)(((unsigned long long)pub_s[10] << 32) | pub_s[9]));
-          Sim3f Tn = T;
-          const int r = timed_out ? 3 : track_update(s_sum, Tn, oc, A.rel_error, A.delta_norm);
-          M3S_TSTAMP(6)
-          if (r != kTrackContinue && r != kTrackConverged) Tn = T;
-          float rec[8];
-          store_sim3(rec, Tn);
-#pragma unroll
-          for (int k = 0; k < 8; k++) pub_s[k] = __float_as_uint(rec[k]);
-          const unsigned long long ob = (unsigned long long)__double_as_longlong(oc);
-          pub_s[8] = (uint32_t)r, pub_s[9] = (uint32_t)(ob & 0xffffffffull), pub_s[10] = (uint32_t)(ob >> 32);
-          pub_s[11] = 0;
-        }
-        wave_lds_fence();
-        const int q = lane < 4 ? 3 * lane : 0;
-        const u32x4 w = {pub_s[q], pub_s[q + 1], pub_s[q + 2], (unsigned)(it + 1)};
-        __builtin_amdgcn_raw_buffer_store_b128(w, Rrec, lane * 16, 0, 16);
-      } else {
-        int spins = 0;
-        u32x4 g;
-        for (;;) {
-          g = poll_b128(Rrec, lane * 16);
-          if (__ballot(lane < 4 && g.w != (unsigned)(it + 1)) == 0) break;
-          trk_pause();
-          if (++spins > kTrkSpins) break;
-        }
-        M3S_TSTAMP(4)
-        if (spins > kTrkSpins) {
-          if (lane == 0) pub_s[8] = 3;
-        } else if (lane < 4) {
-          pub_s[3 * lane] = g.x, pub_s[3 * lane + 1] = g.y, pub_s[3 * lane + 2] = g.z;
-        }
-      }
-    }
-    M3S_TSTAMP(5)
-    __syncthreads();
-    status = (int)pub_s[8];
-    if (status == 3 || status == kTrackFailed) break;
-    T = load_sim3(reinterpret_cast<const float *>(pub_s));
-    if (status == kTrackConverged) break;
-  }
-  if (b == 0 && t == 0) {  // outputs: the last successful pose, the iteration count, the status
-    A.info[M3S_INFO_ITERS] = it < max_iters ? it + 1 : max_iters;
-    if (status == kTrackFailed) A.info[M3S_INFO_SOLVE_FAIL] = 1;
-    if (status == 3) A.info[M3S_INFO_SOLVE_FAIL] = 2;
-    if (status == kTrackConverged) A.info[M3S_INFO_CONVERGED] = 1;
-    store_sim3(st->T_rel, T);
-    store_sim3(A.T_CkCf_out, T);
-    store_sim3(A.T_WCf_out, compose(Tk, T));
-  }
-}
-
-// pixels per lane of the persistent tracker (1, 2, 4) and its workgroup size
-// (threads) so that the grid fits one workgroup per CU; 0: too large (one
-// launch per iteration instead)
-int track_ppl(int64_t HW, int &threads) {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 0;
-    return n;
-  }();
-  const int64_t G = std::min<int64_t>(cus, kTrkMaxBlocks);
-  threads = kTrkThreadsLo;
-  for (int ppl : {1, 2, 4})
-    if (HW <= G * kTrkThreadsLo * ppl) return ppl;
-  threads = kTrkThreadsHi;
-  return HW <= G * kTrkThreadsHi * 4 ? 4 : 0;
-}
-// M3S_TRACK_PERSISTENT=0: one launch per iteration (A/B of the persistent kernel)
-bool track_persistent_enabled() { return knobs().track_persistent != 0; }
-
-int track_impl(const m3s_track_args *a, int mode, void *stream) {
-  if (!a || !a->Xf || !a->Xk || !a->Qk || !a->valid || !a->T_WCf || !a->T_WCk || !a->T_WCf_out ||
-      !a->T_CkCf_out || !a->info || !a->workspace || a->HW < 1)
-    return M3S_EINVAL;
-  if (mode == M3S_MODE_CALIB && (!a->K || a->width < 1 || a->height < 1)) return M3S_EINVAL;
-  if (a->workspace_bytes < m3s_track_workspace_size(a->HW)) return M3S_EINVAL;
-  hipStream_t st = S(stream);
-  ResidualParams P;
-  P.inv_sig_a = (float)(1.0 / (double)a->sigma_a);
-  P.inv_sig_b = (float)(1.0 / (double)a->sigma_b);
-  P.C_thresh = P.Q_thresh = 0.0f;
-  P.fx = P.fy = P.cx = P.cy = 0.0f;
-  P.width = a->width;
-  P.height = a->height;
-  P.border = (float)a->pixel_border;
-  P.z_eps = a->z_eps;
-  P.huber_k = a->huber_k;
-  int rc;
-  if (mode == M3S_MODE_CALIB && (rc = read_K(a->K, P, st))) return rc;
-  TrackState *ts = at<TrackState>(a->workspace, kTrackStateOff);
-  TrackSync *sync = at<TrackSync>(a->workspace, track_sync_off());
-  float *partials = at<float>(a->workspace, track_part_off());
-  int th = kTrkThreadsLo;
-  const int ppl = track_ppl(a->HW, th);
-  const bool persistent = ppl > 0 && track_persistent_enabled();
-  const int G = persistent ? (int)((a->HW + (int64_t)th * ppl - 1) / ((int64_t)th * ppl)) : 0;
-  track_init_kernel<<<1, 256, 0, st>>>(a->T_WCf, a->T_WCk, ts, a->info, a->T_WCf_out, a->T_CkCf_out,
-                                       reinterpret_cast<uint32_t *>(sync), (int)(sizeof(TrackSync) / 4),
-                                       reinterpret_cast<u32x4 *>(partials), G * kTrkGran);
-  if ((rc = launch_ok())) return rc;
-  LinArgs L{};
-  memset(&L, 0, sizeof L);
-  L.T_rel = ts->T_rel;
-  L.Xs = a->Xk;
-  L.Xsrc = a->Xf;
-  L.valid = a->valid;
-  L.Q = a->Qk;
-  L.stop = &ts->done;
-  L.partials = partials;
-  L.HW = a->HW;
-  L.edge_begin = 0;
-  L.chunks = chunks_for(a->HW, 1);
-  L.chunk_pix = chunk_pixels(a->HW, L.chunks);
-  L.P = P;
-  L.Kd = nullptr;  // the tracker passes its intrinsics in P
-  L.track = ts;  // one launch per iteration: the last chunk runs the solve
-  L.info = a->info;
-  L.T_WCf_out = a->T_WCf_out, L.T_CkCf_out = a->T_CkCf_out;
-  L.rel_error = a->rel_error, L.delta_norm = a->delta_norm;
-  const bool vec = (a->HW % 4 == 0) && vec_ok(a->Xf, 16) && vec_ok(a->Xk, 16) && vec_ok(a->Qk, 16) &&
-                   vec_ok(a->valid, 4);
-  // persistent: every iteration in one launch (one workgroup per CU)
-  if (persistent) {
-    if (a->max_iters < 1) return M3S_OK;
-    if (mode == M3S_MODE_RAYS) {
-      if (th == kTrkThreadsHi) track_persistent_kernel<M3S_MODE_RAYS, 4, kTrkThreadsHi><<<G, th, 0, st>>>(L, a->max_iters, sync);
-      else if (ppl == 1) track_persistent_kernel<M3S_MODE_RAYS, 1, kTrkThreadsLo><<<G, th, 0, st>>>(L, a->max_iters, sync);
-      else if (ppl == 2) track_persistent_kernel<M3S_MODE_RAYS, 2, kTrkThreadsLo><<<G, th, 0, st>>>(L, a->max_iters, sync);
-      else track_persistent_kernel<M3S_MODE_RAYS, 4, kTrkThreadsLo><<<G, th, 0, st>>>(L, a->max_iters, sync);
-    } else {
-      if (th == kTrkThreadsHi) track_persistent_kernel<M3S_MODE_CALIB, 4, kTrkThreadsHi><<<G, th, 0, st>>>(L, a->max_iters, sync);
-      else if (ppl == 1) track_persistent_kernel<M3S_MODE_CALIB, 1, kTrkThreadsLo><<<G, th, 0, st>>>(L, a->max_iters, sync);
-      else if (ppl == 2) track_persistent_kernel<M3S_MODE_CALIB, 2, kTrkThreadsLo><<<G, th, 0, st>>>(L, a->max_iters, sync);
-      else track_persistent_kernel<M3S_MODE_CALIB, 4, kTrkThreadsLo><<<G, th, 0, st>>>(L, a->max_iters, sync);
-    }
-    return launch_ok();
-  }
-  for (int it = 0; it < a->max_iters; it++) {
-    if ((rc = dispatch_linearize<true>(mode, L, L.chunks, vec, 0, st))) return rc;
-    if (a->sync_every > 0 && (it + 1) % a->sync_every == 0 && it + 1 < a->max_iters) {
-      int32_t done = 0;
-      if (hipMemcpyAsync(&done, &ts->done, sizeof done, hipMemcpyDeviceToHost, st) != hipSuccess)
-        return M3S_ELAUNCH;
-      if (hipStreamSynchronize(st) != hipSuccess) return M3S_ELAUNCH;
-      if (done) break;
-    }
-  }
-  return M3S_OK;
-}
-
-// ------------------------------------------------------ track_frame prep --
-// The front end of FrameTracker.track (tracker.py:41-67, 103-108, 129-154)
-// ahead of the tracker launches above: three small launches per call.
-//   1 track_prep_clear_kernel  zeroes the occupancy map and stats[0..3]
-//   2 track_prep_kernel        one lane per keyframe pixel n, j = idx_f2k[n]:
-//       Xf_g[n] = Xf_canon[j] (calib: constrained to the ray of pixel j, the
-//       operation order of backproject, geometry.py:107-115: divide, then
-//       multiply), Xk_g[n] likewise from Xk_canon[n], valid_opt[n], and
-//       map[j] = 1 where valid_match[n]: a byte map of the frame's pixels
-//       written with plain stores (every writer stores the same 1, so the
-//       stores need no order). n_opt and n_kf: a wave ballot and popcount,
-//       summed over the workgroup's waves in LDS, one integer atomic add per
-//       workgroup and counter (integer sums have no order: deterministic).
-//   3 track_prep_count_kernel  n_unique = the number of set bytes of the map,
-//       16 map bytes per lane, one integer atomic add per workgroup.
-// No sort and no compaction: torch.unique(idx[valid]).shape[0] is the number
-// of frame pixels hit at least once. Nothing is carried between calls: launch
-// 1 clears every word launches 2 and 3 read.
-constexpr int kPrepThreads = 256;
-constexpr int kPrepWaves = kPrepThreads / 64;
-constexpr int kPrepMapPerLane = 16;  // map bytes per lane and access (one dwordx4)
-
-struct PrepArgs {
-  const float *Xf_canon, *Cf_sum, *Xk_canon, *Ck_sum, *Qk;
-  const float *K;  // device 3x3; null: rays mode (rows copied as they are)
-  const int32_t *idx;
-  const uint8_t *valid_match;
-  float *Xf_g;
-  float *Xk_g;  // null: the keyframe rows are not written (rays mode reads Xk_canon itself)
-  uint8_t *valid_opt;
-  uint8_t *map;  // [map_bytes(HW)]
-  int32_t *stats;
-  int64_t HW;
-  int W;
-  float Nf, Nk, C_conf, Q_conf;
-};
-
-inline size_t prep_map_bytes(int64_t HW) { return align_up((size_t)HW, kPrepMapPerLane); }
-
-__global__ void __launch_bounds__(kPrepThreads) track_prep_clear_kernel(u32x4 *map, int64_t n16, int32_t *stats) {
-  const int64_t stride = (int64_t)gridDim.x * kPrepThreads;
-  for (int64_t k = (int64_t)blockIdx.x * kPrepThreads + threadIdx.x; k < n16; k += stride)
-    map[k] = u32x4{0u, 0u, 0u, 0u};
-  if (blockIdx.x == 0 && threadIdx.x < 4) stats[threadIdx.x] = 0;
-}
-
-// sum of one int per lane over the workgroup (every lane of every wave calls
-// it); the result is valid in thread 0
-__device__ __forceinline__ int prep_block_sum(int c, int *sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-  __syncthreads();
-  int s = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kPrepWaves; w++) s += sh[w];
-  return s;
-}
-
-__global__ void __launch_bounds__(kPrepThreads) track_prep_kernel(PrepArgs A) {
-  __shared__ int sh[2][kPrepWaves];
-  const int64_t n = (int64_t)blockIdx.x * kPrepThreads + threadIdx.x;
-  bool opt = false, kf = false;
-  if (n < A.HW) {  // no early return: every lane reaches the ballots and the barrier
-    int64_t j = A.idx[n];
-    bool vm = A.valid_match[n] != 0;
-    // idx_f2k in [0, HW) is the caller's contract; a value outside it is never
-    // used as an address
-    if (j < 0 || j >= A.HW) j = 0, vm = false;
-    const float q = A.Qk[n];
-    const float cf = A.Cf_sum[j] / A.Nf, ck = A.Ck_sum[n] / A.Nk;  // frame.py:102-103
-    kf = vm && q > A.Q_conf;
-    opt = kf && cf > A.C_conf && ck > A.C_conf;
-    float xf = A.Xf_canon[3 * j], yf = A.Xf_canon[3 * j + 1];
-    const float zf = A.Xf_canon[3 * j + 2];
-    float fx = 1.0f, fy = 1.0f, cx = 0.0f, cy = 0.0f;
-    if (A.K) {
-      fx = A.K[0], fy = A.K[4], cx = A.K[2], cy = A.K[5];
-      const int v = (int)j / A.W, u = (int)j - v * A.W;  // j < HW <= INT32_MAX
-      xf = zf * (((float)u - cx) / fx);
-      yf = zf * (((float)v - cy) / fy);
-    }
-    A.Xf_g[3 * n] = xf, A.Xf_g[3 * n + 1] = yf, A.Xf_g[3 * n + 2] = zf;
-    if (A.Xk_g) {
-      float xk = A.Xk_canon[3 * n], yk = A.Xk_canon[3 * n + 1];
-      const float zk = A.Xk_canon[3 * n + 2];
-      if (A.K) {
-        const int v = (int)n / A.W, u = (int)n - v * A.W;
-        xk = zk * (((float)u - cx) / fx);
-        yk = zk * (((float)v - cy) / fy);
-      }
-      A.Xk_g[3 * n] = xk, A.Xk_g[3 * n + 1] = yk, A.Xk_g[3 * n + 2] = zk;
-    }
-    A.valid_opt[n] = opt ? 1 : 0;
-    if (vm) A.map[j] = 1;
-  }
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-  const uint64_t m_opt = __builtin_amdgcn_ballot_w64(opt), m_kf = __builtin_amdgcn_ballot_w64(kf);
-  if (lane == 0) sh[0][wave] = (int)__builtin_popcountll(m_opt), sh[1][wave] = (int)__builtin_popcountll(m_kf);
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    int s = 0;
-    for (int w = 0; w < kPrepWaves; w++) s += sh[threadIdx.x][w];
-    if (s) atomicAdd(&A.stats[threadIdx.x], s);
-  }
-}
-
-__global__ void __launch_bounds__(kPrepThreads) track_prep_count_kernel(const u32x4 *map, int64_t n16,
-                                                                        int32_t *stats) {
-  __shared__ int sh[kPrepWaves];
-  const int64_t k = (int64_t)blockIdx.x * kPrepThreads + threadIdx.x;
-  int c = 0;
-  if (k < n16) {
-    const u32x4 w = map[k];  // bytes are 0 or 1
-    c = __builtin_popcount(w.x) + __builtin_popcount(w.y) + __builtin_popcount(w.z) + __builtin_popcount(w.w);
-  }
-  const int s = prep_block_sum(c, sh);
-  if (threadIdx.x == 0 && s) atomicAdd(&stats[2], s);
-}
-
-// workspace of m3s_track_frame: the tracker's own workspace first (handed to
-// track_impl unchanged), then the map and the prepared rows
-struct FrameLayout {
-  size_t track, map, xf, xk, valid, total;
-};
-FrameLayout frame_layout(int64_t HW) {
-  FrameLayout L;
-  const size_t hw = (size_t)std::max<int64_t>(HW, 0);
-  L.track = 0;
-  L.map = align_up(m3s_track_workspace_size(HW), 256);
-  L.xf = L.map + align_up(prep_map_bytes(hw), 256);
-  L.xk = L.xf + align_up(12 * hw, 256);
-  L.valid = L.xk + align_up(12 * hw, 256);
-  L.total = L.valid + align_up(hw, 256);
-  return L;
-}
-
-int track_frame_impl(const m3s_track_frame_args *a, void *stream) {
-  if (!a || !a->Xf_canon || !a->Cf_sum || !a->Xk_canon || !a->Ck_sum || !a->idx_f2k || !a->valid_match ||
-      !a->Qk || !a->T_WCf || !a->T_WCk || !a->T_WCf_out || !a->T_CkCf_out || !a->info || !a->stats ||
-      !a->workspace)
-    return M3S_EINVAL;
-  if (a->HW < 1 || a->height < 1 || a->width < 1 || a->HW != (int64_t)a->height * a->width) return M3S_EINVAL;
-  if (a->HW > INT32_MAX) return M3S_ETOOLARGE;  // idx_f2k is int32
-  if (a->Nf < 1 || a->Nk < 1) return M3S_EINVAL;
-  const FrameLayout Ly = frame_layout(a->HW);
-  if (a->workspace_bytes < Ly.total) return M3S_EINVAL;
-  const bool calib = a->K != nullptr;
-  hipStream_t st = S(stream);
-  float *Xf_g = a->Xf_out ? a->Xf_out : at<float>(a->workspace, Ly.xf);
-  // rays mode: the keyframe rows are Xk_canon as it is; they are copied only
-  // into a buffer the caller asks for (and not onto themselves)
-  float *Xk_g = a->Xk_out ? a->Xk_out : (calib ? at<float>(a->workspace, Ly.xk) : nullptr);
-  if (!calib && Xk_g == a->Xk_canon) Xk_g = nullptr;
-  uint8_t *valid_opt = a->valid_opt_out ? a->valid_opt_out : at<uint8_t>(a->workspace, Ly.valid);
-  uint8_t *map = at<uint8_t>(a->workspace, Ly.map);
-  const int64_t n16 = (int64_t)(prep_map_bytes(a->HW) / kPrepMapPerLane);
-  const int64_t count_blocks = (n16 + kPrepThreads - 1) / kPrepThreads;
-  track_prep_clear_kernel<<<(unsigned)std::min<int64_t>(count_blocks, 256), kPrepThreads, 0, st>>>(
-      reinterpret_cast<u32x4 *>(map), n16, a->stats);
-  int rc;
-  if ((rc = launch_ok())) return rc;
-  PrepArgs A{};
-  A.Xf_canon = a->Xf_canon, A.Cf_sum = a->Cf_sum, A.Xk_canon = a->Xk_canon, A.Ck_sum = a->Ck_sum;
-  A.Qk = a->Qk, A.K = a->K, A.idx = a->idx_f2k, A.valid_match = a->valid_match;
-  A.Xf_g = Xf_g, A.Xk_g = Xk_g, A.valid_opt = valid_opt, A.map = map, A.stats = a->stats;
-  A.HW = a->HW, A.W = a->width;
-  A.Nf = (float)a->Nf, A.Nk = (float)a->Nk, A.C_conf = a->C_conf, A.Q_conf = a->Q_conf;
-  track_prep_kernel<<<(unsigned)((a->HW + kPrepThreads - 1) / kPrepThreads), kPrepThreads, 0, st>>>(A);
-  if ((rc = launch_ok())) return rc;
-  track_prep_count_kernel<<<(unsigned)count_blocks, kPrepThreads, 0, st>>>(reinterpret_cast<const u32x4 *>(map),
-                                                                          n16, a->stats);
-  if ((rc = launch_ok())) return rc;
-  // the launches of m3s_track_{rays,calib}_sim3 on the prepared rows
-  m3s_track_args t{};
-  t.Xf = Xf_g, t.Xk = Xk_g ? Xk_g : a->Xk_canon, t.Qk = a->Qk, t.valid = valid_opt;
-  t.T_WCf = a->T_WCf, t.T_WCk = a->T_WCk, t.K = a->K;
-  t.HW = a->HW;
-  t.height = calib ? a->height : 0, t.width = calib ? a->width : 0;
-  t.pixel_border = a->pixel_border, t.z_eps = a->z_eps;
-  t.sigma_a = a->sigma_a, t.sigma_b = a->sigma_b, t.huber_k = a->huber_k;
-  t.max_iters = a->max_iters, t.rel_error = a->rel_error, t.delta_norm = a->delta_norm;
-  t.sync_every = a->sync_every;
-  t.T_WCf_out = a->T_WCf_out, t.T_CkCf_out = a->T_CkCf_out, t.info = a->info;
-  t.workspace = at<void>(a->workspace, Ly.track);
-  t.workspace_bytes = Ly.map;
-  return track_impl(&t, calib ? M3S_MODE_CALIB : M3S_MODE_RAYS, stream);
-}
+namespace {
 
 // Streaming copy (m3s_debug_copy): the measured HBM ceiling bench.py reports
 // beside the 8 TB/s spec. 16 B per lane per access (dwordx4), 4 accesses in
@@ -6985,38 +6341,7 @@ int m3s_debug_stamps(int which, int64_t *out) {
 
 int m3s_set_knob(const char *name, int value) {
   if (!name) return M3S_EINVAL;
-  Knobs &k = knobs();
-  const struct {
-    const char *n;
-    std::atomic<int> *v;
-  } tab[] = {{"plan_cache", &k.plan_cache}, {"dense_tail_min", &k.dense_tail_min},
-             {"track_persistent", &k.track_persistent}, {"prologue", &k.prologue},
-#ifdef M3S_TEST_PATHS
-             {"dense", &k.dense}, {"cols", &k.cols}, {"df", &k.df}, {"tail_cyc", &k.tail_cyc},
-             {"tail_mfma", &k.tail_mfma}, {"border_split", &k.border_split}, {"debug_drop_item", &k.debug_drop_item},
-             {"gather_lds", &k.gather_lds}, {"tail_pair", &k.tail_pair}, {"tail_warm", &k.tail_warm},
-             {"gcomb", &k.gcomb}, {"gcomb_wg", &k.gcomb_wg}, {"gcomb_min_nc", &k.gcomb_min_nc}
-#endif
-  };
-  for (const auto &t : tab)
-    if (std::strcmp(t.n, name) == 0) {
-      const int old = t.v->exchange(value);
-      // knobs that shape a plan (its schedule, split lists, tail, path) are
-      // not all in the plan-cache key: a change drops every cached plan, so
-      // no launch reads a plan built for another path (e.g. a chip-path
-      // plan, cached unscheduled, on the one-workgroup kernel)
-      static const char *const shaping[] = {"dense_tail_min", "dense", "cols", "df", "tail_cyc",
-                                            "tail_mfma", "border_split", "debug_drop_item"};
-      if (old != value)
-        for (const char *sn : shaping)
-          if (std::strcmp(sn, name) == 0) {
-            std::lock_guard<std::mutex> g(g_cache_mu);
-            g_cache.clear();
-            break;
-          }
-      return old;
-    }
-  return -(1 << 30);
+  return set_knob(name, value);
 }
 
 int m3s_debug_call_timing(int enable) {

@@ -1,5 +1,5 @@
 """GPU checks of track_frame (mast3r_slam_backends.track_frame ->
-m3s_track_frame, csrc/m3s_gn.hip) and of mast3r_slam_amd.tracker.FrameTracker.
+m3s_track_frame, csrc/gn/track_frame.h) and of mast3r_slam_amd.tracker.FrameTracker.
 
 References:
 
