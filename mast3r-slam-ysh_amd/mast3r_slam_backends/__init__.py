@@ -33,6 +33,10 @@ binarise, pack), search (Hamming similarity, scores, top-k) and append, on an
 ``asmk_centroid_norms`` and ``asmk_quantize`` are that quantize itself as a
 fused distance and top-MA kernel (no distance matrix), for callers without torch
 and for ``RetrievalDatabase(quantizer="device")``.
+
+``rope_2d`` (new; include/m3s_rope.h) is the 2-D rotary position embedding of
+MASt3R's attention, in place on the q or k slice of a qkv buffer, one launch;
+``mast3r_slam_amd.rope`` puts it into a loaded model.
 """
 from __future__ import annotations
 
@@ -242,6 +246,22 @@ class AsmkQuantizeArgs(ctypes.Structure):
     ]
 
 
+# every symbol include/m3s_rope.h declares
+ROPE_EXPORTS = ("m3s_rope_2d",)
+ROPE_F32, ROPE_F16, ROPE_BF16 = 0, 1, 2
+
+
+class RopeArgs(ctypes.Structure):
+    """Mirror of ``m3s_rope_args`` (include/m3s_rope.h)."""
+
+    _fields_ = [
+        ("tokens", _VP), ("pos", _VP),
+        ("B", ctypes.c_int64), ("N", ctypes.c_int64), ("H", ctypes.c_int64), ("D", ctypes.c_int64),
+        ("stride_b", ctypes.c_int64), ("stride_n", ctypes.c_int64),
+        ("base", ctypes.c_float), ("f0", ctypes.c_float), ("dtype", ctypes.c_int),
+    ]
+
+
 def _load(path=LIB_PATH):
     if not os.path.exists(path):
         raise ImportError(
@@ -318,6 +338,8 @@ def _load(path=LIB_PATH):
             fn.argtypes = [P({"m3s_asmk_aggregate": AsmkAggregateArgs,
                               "m3s_asmk_search": AsmkSearchArgs,
                               "m3s_asmk_quantize": AsmkQuantizeArgs}.get(f, AsmkDb)), _VP]
+    lib.m3s_rope_2d.restype = ctypes.c_int  # include/m3s_rope.h
+    lib.m3s_rope_2d.argtypes = [P(RopeArgs), _VP]
     return lib
 
 
@@ -807,6 +829,60 @@ def prep_rays(X11, X21):
     a.X11, a.X21, a.B, a.H, a.W, a.rays_img, a.pts_norm = _p(X11), _p(X21), B, H, W, _p(rays), _p(pts)
     _raise(_lib.m3s_prep_rays(ctypes.byref(a), _stream(dev)), "m3s_prep_rays")
     return rays, pts
+
+
+# --------------------------------------------------------------- rope ---
+_ROPE_DTYPES = {torch.float32: ROPE_F32, torch.float16: ROPE_F16, torch.bfloat16: ROPE_BF16}
+
+
+def rope_2d(tokens, positions, base, f0):
+    """2-D rotary position embedding, in place (new entry point; m3s_rope_2d;
+    RoPE2D of croco's models/pos_embed.py:112-159, which the reference runs
+    through its curope extension).
+
+    tokens: the [B, N, H, D] view of q or k, float32, float16 or bfloat16, D a
+    multiple of 4, a head row contiguous and the heads of a token back to back
+    (stride(3) == 1, stride(2) == D); the token and batch strides are free, so
+    ``qkv[:, :, i].transpose(1, 2)`` of an attention's [B, H, 3, N, D] view is
+    taken as it is. positions [B, N, 2] int64, (y, x) per token. The angle of
+    frequency i of an axis is position * f0 / base^(i / (D/4)), evaluated in
+    fp32; the result is rounded once to the tokens' dtype. f0 -> -f0 undoes the
+    rotation. One launch, no host synchronisation. Returns tokens."""
+    if not isinstance(tokens, torch.Tensor) or not isinstance(positions, torch.Tensor):
+        raise RuntimeError("rope_2d: tokens and positions must be tensors")
+    # layout and dtype first, the device last, in the order of _check
+    if tokens.dtype not in _ROPE_DTYPES:
+        raise RuntimeError(f"tokens must be float32, float16 or bfloat16 (got {tokens.dtype})")
+    if tokens.dim() != 4:
+        raise RuntimeError(f"tokens must be [B, N, H, D] (got {tuple(tokens.shape)})")
+    B, N, H, D = (int(x) for x in tokens.shape)
+    if D % 4 != 0:
+        raise RuntimeError(f"rope_2d: D = {D} is not a multiple of 4")
+    if tokens.numel() and (tokens.stride(3) != 1 or (H > 1 and tokens.stride(2) != D)):
+        raise RuntimeError("tokens: a head row must be contiguous and the heads of a token back to back "
+                           "(stride(3) == 1, stride(2) == D)")
+    if positions.dtype != torch.int64:
+        raise RuntimeError(f"positions must be {torch.int64} (got {positions.dtype})")
+    if tuple(positions.shape) != (B, N, 2):
+        raise RuntimeError(f"positions must be [{B}, {N}, 2] (got {tuple(positions.shape)})")
+    if not positions.is_contiguous():
+        raise RuntimeError("positions must be contiguous")
+    if tokens.device.type != "cuda":
+        raise RuntimeError(f"tokens must be on a ROCm device (got {tokens.device}); no CPU path")
+    if positions.device != tokens.device:
+        raise RuntimeError(f"rope_2d: positions is on {positions.device}, tokens on {tokens.device}")
+    if tokens.numel() == 0:
+        return tokens
+    row = H * D
+    a = RopeArgs()
+    a.tokens, a.pos = _p(tokens), _p(positions)
+    a.B, a.N, a.H, a.D = B, N, H, D
+    # the stride of a dimension of size 1 is arbitrary: give it the dense value
+    a.stride_n = tokens.stride(1) if N > 1 else row
+    a.stride_b = tokens.stride(0) if B > 1 else (N - 1) * a.stride_n + row
+    a.base, a.f0, a.dtype = float(base), float(f0), _ROPE_DTYPES[tokens.dtype]
+    _raise(_lib.m3s_rope_2d(ctypes.byref(a), _stream(tokens.device)), "m3s_rope_2d")
+    return tokens
 
 
 # ---------------------------------------------------------- retrieval ---
