@@ -1,0 +1,603 @@
+// gn/plan.h — part of the m3s_gn.hip translation unit (not a stand-alone header).
+// From edge ids to a plan on the device: PlanMeta and the workspace registry,
+// pinned staging, the plan cache, set_knob, build_plan_meta, build_eorder,
+// upload_plan, gn_prepare_impl (host prepare), finish_plan / host_finish and
+// gn_prepare_async (the prologue launch).
+// Relies on m3s_gn.hip above the include list (Layout / gn_layout,
+// kStageDoubles, kSplitUpdates, the call prologue, S, launch_ok) and on
+// gn/knobs.h; declares set_lds_attributes_once, which gn/iterate.h defines.
+
+struct PlanMeta {
+  int epoch = 0;  // solve launches since m3s_gn_prepare (column-task flags / tickets)
+  bool sparse = false;
+  int store = 0;  // sparse_llt_kernel<STORE>
+  bool asm_lds = false;  // LDS factor with room for the staged fin blocks: assembly in the LLT kernel
+  size_t lds_bytes = 0;
+  int m = 0, S = 0, levels = 0, plan_len = 0, n_items = 0, n_tasks = 0, n_parts = 0, nc = 0;
+  int nnz = 0;  // off-diagonal blocks (col_ptr[m])
+  int off_dfitems = 0, n_dfitems = 0;  // df_factor_kernel dispatch list (appended to the plan image)
+  int n_dfsparse = 0;                  // its sparse-column items (the border items follow)
+  PlanImage img;  // offsets (data vector cleared after upload)
+  // linearize state of this solve call: edge ranks, the task table of the
+  // edge range last linearized (host copy stays alive for the async upload)
+  // and whether that range's planes are stored
+  std::vector<int32_t> rj, h_ri;   // edge ranks (host copies of the uploaded arrays)
+  std::vector<int32_t> h_plan;     // flattened plan (host copy of the upload)
+  int32_t h_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int32_t h_flags[64] = {0};
+  bool has_K = false;
+  float K4[4] = {0.f, 0.f, 0.f, 0.f};  // fx, fy, cx, cy (calib; read once per call)
+  int64_t range_b = -1, range_e = -1;  // the edge range last linearized
+  bool order_ok = false;               // its edge order is in the workspace (Layout::eorder)
+  bool planes_ok = false;
+  // stepwise linearize with fused edge sums: edge_cnt arrivals counted since
+  // the counters were last zeroed (valid for every edge of the range); false:
+  // the counters hold arrivals of another range or of a drop-in call
+  uint32_t cnt_arr = 0;
+  bool cnt_ok = true;
+  std::vector<int32_t> eorder;         // host copy of the full range's order (host prepare)
+  // the symbolic plan of this call is built by its first solve (cache miss at
+  // prepare): the host analysis then overlaps the first linearize kernel
+  bool plan_pending = false;
+  bool force_dense = false;
+  // the ids of this call are still on their way to the host (device prologue,
+  // gn_prepare_async): host_finish reads them from pinned slot `slot`
+  bool host_pending = false;
+  int slot = -1;
+};
+
+// What a solve launch reads of the registry entry: the scalars and plan
+// offsets, not the host vectors (ranks, task tables, plan image) that the
+// entry keeps alive for queued uploads.
+PlanMeta solve_view(const PlanMeta &M) {
+  PlanMeta v;
+  v.epoch = M.epoch, v.sparse = M.sparse, v.store = M.store, v.asm_lds = M.asm_lds, v.lds_bytes = M.lds_bytes;
+  v.m = M.m, v.S = M.S, v.levels = M.levels, v.plan_len = M.plan_len, v.n_items = M.n_items;
+  v.n_tasks = M.n_tasks, v.n_parts = M.n_parts, v.nc = M.nc, v.off_dfitems = M.off_dfitems;
+  v.n_dfitems = M.n_dfitems;
+  v.n_dfsparse = M.n_dfsparse;
+  v.nnz = M.nnz;
+  v.img = M.img;  // offsets (its data vector is empty in the registry)
+  v.plan_pending = M.plan_pending;
+  return v;
+}
+// Host registry of the per-call plan (keyed by workspace): the stepwise API
+// calls prepare and solve separately.
+std::mutex g_reg_mu;
+std::unordered_map<const void *, PlanMeta> g_reg;
+
+// Pinned host staging of the per-call transfers (gn_prepare_impl: the D2H
+// reads of K, ii, jj and ONE H2D upload of flags | ranks | task table | plan;
+// finish_plan: a deferred plan; gn_linearize_impl: a sharded rank's task
+// table). Pageable copies were one staged, host-synchronous transfer each
+// (~7 per call); an event per buffer guards it until the copy that reads it
+// has left. The registry entries own no memory a queued copy still reads.
+// Pinned slot the device prologue writes a call's ii, jj and K into (host-
+// mapped); busy from the prepare until the host has read it (host_finish or
+// release), its event marks the prologue's completion.
+struct DownSlot {
+  char *p = nullptr, *dp = nullptr;  // host / device view
+  size_t cap = 0;
+  hipEvent_t ev = nullptr;
+  bool busy = false, used = false;
+};
+struct Staging {
+  char *down = nullptr, *up = nullptr, *plan_up = nullptr, *tasks_up = nullptr;
+  size_t down_cap = 0, up_cap = 0, plan_cap = 0, tasks_cap = 0;
+  hipEvent_t ev = nullptr, plan_ev = nullptr, tasks_ev = nullptr;
+  bool pending = false, plan_pending = false, tasks_pending = false;
+  hipStream_t side = nullptr;  // plan uploads that must not queue behind a running linearize
+  std::vector<DownSlot> slots;
+};
+// One staging set per device: an event recorded on one device's stream cannot
+// guard another device's copies (a process may drive GN on several GPUs).
+std::mutex g_stage_mu;
+std::unordered_map<int, Staging> g_stages;
+bool pinned_reserve(char *&p, size_t &cap, size_t need) {
+  if (need <= cap) return true;
+  if (p) (void)hipHostFree(p);
+  p = nullptr, cap = 0;
+  const size_t n = std::max<size_t>(need + need / 2, 1 << 16);
+  if (hipHostMalloc(reinterpret_cast<void **>(&p), n, hipHostMallocDefault) != hipSuccess) return false;
+  cap = n;
+  return true;
+}
+Staging *stage_for_device() {  // caller holds g_stage_mu
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  Staging &S = g_stages[dev];
+  for (hipEvent_t *e : {&S.ev, &S.plan_ev, &S.tasks_ev})
+    if (!*e && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return nullptr;
+  if (!S.side && hipStreamCreateWithFlags(&S.side, hipStreamNonBlocking) != hipSuccess) return nullptr;
+  return &S;
+}
+// A free pinned slot of at least `need` bytes (caller holds g_stage_mu).
+int acquire_slot(Staging &SG, size_t need) {
+  int k = -1;
+  for (int q = 0; q < (int)SG.slots.size(); q++)
+    if (!SG.slots[q].busy) {
+      k = q;
+      break;
+    }
+  if (k < 0) {
+    SG.slots.emplace_back();
+    k = (int)SG.slots.size() - 1;
+  }
+  DownSlot &D = SG.slots[k];
+  if (D.used && hipEventSynchronize(D.ev) != hipSuccess) return -1;  // its last prologue has finished writing
+  if (!D.ev && hipEventCreateWithFlags(&D.ev, hipEventDisableTiming) != hipSuccess) return -1;
+  if (need > D.cap) {
+    if (D.p) (void)hipHostFree(D.p);
+    D.p = D.dp = nullptr, D.cap = 0;
+    const size_t n = std::max<size_t>(need + need / 2, 1 << 16);
+    if (hipHostMalloc(reinterpret_cast<void **>(&D.p), n, hipHostMallocDefault) != hipSuccess) return -1;
+    void *dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, D.p, 0) != hipSuccess) return -1;
+    D.dp = static_cast<char *>(dp), D.cap = n;
+  }
+  D.busy = true, D.used = true;
+  return k;
+}
+
+// Linearize edge order of an edge range: its edges (local indices) sorted by
+// KF j (block_task deals the (chunk, KF j)-sorted tasks over the XCDs).
+void build_eorder(const std::vector<int32_t> &rj, int64_t eb, int64_t E_loc, std::vector<int32_t> &out) {
+  out.resize((size_t)E_loc);
+  for (int64_t e = 0; e < E_loc; e++) out[e] = (int32_t)e;
+  std::stable_sort(out.begin(), out.end(), [&](int32_t x, int32_t y) { return rj[eb + x] < rj[eb + y]; });
+}
+
+constexpr size_t kMaxLdsBytes = 150 * 1024;
+// Defined behind gn_solve_impl: its body names the sparse_llt_kernel
+// specialisations, and where a kernel template is first named decides its
+// place in the device code (the order rule, m3s_gn.hip).
+void set_lds_attributes_once();
+
+// Host symbolic plans of recent edge sets (the same factor graph is usually
+// solved many times: every keyframe's local/global optimisation, every bench
+// step). Keyed by (N, HW, E, dense override, remapped ranks).
+struct PlanCacheEntry {
+  int64_t N = 0, HW = 0, E = 0;
+  bool dense = false;
+  int tail_min = 0;  // dense_tail_min() the plan was built with
+  std::vector<int32_t> ri, rj;
+  PlanMeta meta;
+};
+std::mutex g_cache_mu;
+std::vector<PlanCacheEntry> g_cache;  // most recent first
+constexpr size_t kPlanCacheSize = 4;
+
+// m3s_set_knob: the previous value, or -(1 << 30) for a name this build does
+// not know. A plan-shaping knob set to a different value drops the plan cache.
+int set_knob(const char *name, int value) {
+  Knobs &K = knobs();
+  for (int k = 0; k < kNumKnobs; k++)
+    if (std::strcmp(kKnobDefs[k].name, name) == 0) {
+      const int old = K.v[k].exchange(value);
+      if (kKnobDefs[k].shaping && old != value) {
+        std::lock_guard<std::mutex> g(g_cache_mu);
+        g_cache.clear();
+      }
+      return old;
+    }
+  return -(1 << 30);
+}
+
+// Symbolic plan + LDS budget + full-range task table for remapped ranks.
+PlanMeta build_plan_meta(const m3s_gn_args *a, const Layout &Ly, const std::vector<int32_t> &ri,
+                         const std::vector<int32_t> &rj, bool force_dense) {
+  PlanMeta meta;
+  const int64_t E = a->E;
+  if (a->N > 1) {
+    SparsePlan P;
+    // The dispatch schedule (witems) and the split update lists (PART items)
+    // serve only the one-workgroup sparse_llt_kernel; a factor in global
+    // memory on the chip-wide path (df_factor / tail / column back-
+    // substitution) needs neither: at 256 KFs that halves the host analysis.
+    build_sparse_plan((int)a->N, ri, rj, P, 0, 0, dense_tail_min(), false);
+    const bool global_factor = sizeof(double) * ((size_t)(P.S + P.m) * 49 + (size_t)P.m * 7) > kMaxLdsBytes;
+    const bool chip_path = global_factor && cols_path() && P.m <= 512 && (P.nc == 0 || 7 * P.nc + 1 <= 16 * kTailMaxT);
+    if (global_factor && !chip_path)  // split long update lists for the staged global-factor products
+      build_sparse_plan((int)a->N, ri, rj, P, kSplitUpdates, Ly.slot_cap - 1, dense_tail_min(), true);
+    else if (!chip_path)
+      schedule_plan_items(P);
+    PlanImage img;
+    flatten_plan(P, img);
+    // df_factor_kernel's dispatch list: the sparse columns in level order,
+    // DIAG(k) then the OFF tasks of column k, then the dense-tail border tasks
+    meta.off_dfitems = (int)img.data.size();
+    for (int32_t k : P.corder) {
+      img.data.push_back(-1 - k);
+      for (int q = 0; q < P.col_ptr[k + 1] - P.col_ptr[k]; q++) img.data.push_back(P.ctask0[k] + q);
+    }
+    meta.n_dfsparse = (int)img.data.size() - meta.off_dfitems;
+    for (int b = 0; b < P.nc * (P.nc + 1) / 2; b++) img.data.push_back((int32_t)P.task_dst.size() + b);
+    meta.n_dfitems = (int)img.data.size() - meta.off_dfitems;
+    const bool fits = (int64_t)img.data.size() <= Ly.plan_cap && P.S <= Ly.slot_cap;
+    if (fits && !force_dense) {
+      meta.sparse = true;
+      meta.m = P.m;
+      meta.S = P.S;
+      meta.levels = P.levels;
+      meta.plan_len = (int)img.data.size();
+      meta.n_items = (int)P.items.size();
+      meta.n_tasks = (int)P.task_dst.size();
+      meta.n_parts = (int)P.part_q0.size();
+      meta.nc = P.nc;
+      meta.nnz = P.col_ptr.empty() ? 0 : P.col_ptr[P.m];
+      // LDS plan of sparse_llt_kernel<STORE>: flags always, factor + W + y if
+      // they fit, the plan too if it fits as well; else global factor with
+      // per-wave stage areas
+      const size_t flags_bytes =
+          sizeof(int32_t) * (((size_t)(P.S + 2 * P.m + P.part_q0.size()) + 1) & ~size_t(1));
+      const size_t fac_bytes = sizeof(double) * ((size_t)(P.S + P.m) * 49 + (size_t)P.m * 7);
+      const size_t plan_bytes = sizeof(int32_t) * ((img.data.size() + 1) & ~size_t(1));
+      const size_t stage_bytes = sizeof(double) * 16 * (size_t)kStageDoubles;
+      const size_t fin_bytes = sizeof(double) * kFin * (size_t)E;
+      if (fac_bytes + plan_bytes + flags_bytes <= kMaxLdsBytes) {
+        meta.store = 1;
+        meta.lds_bytes = fac_bytes + plan_bytes + flags_bytes;
+      } else if (fac_bytes + flags_bytes <= kMaxLdsBytes) {
+        meta.store = 2;
+        meta.lds_bytes = fac_bytes + flags_bytes;
+      }
+      if (meta.store != 0 && meta.lds_bytes + fin_bytes <= kMaxLdsBytes) {
+        meta.asm_lds = true;
+        meta.lds_bytes += fin_bytes;
+      }
+      if (meta.store == 0) {
+        meta.store = 0;
+        meta.lds_bytes = sizeof(double) * (size_t)P.m * 7 + flags_bytes + stage_bytes;
+        if (meta.lds_bytes > kMaxLdsBytes) meta.sparse = false;  // dense fallback
+      }
+      meta.h_plan = std::move(img.data);
+      img.data.clear();
+      meta.img = img;
+    }
+  }
+  (void)E;
+  return meta;
+}
+
+// The per-call flag state the solve kernels of a plan rely on: the column-
+// task / dataflow / dense-tail epoch flags live only on the global-factor
+// path (the LDS-resident factors keep theirs in LDS), and no tagged granule
+// of an earlier call may match this call's epochs.
+bool reset_plan_flags(const PlanMeta &M, const Layout &Ly, void *ws, hipStream_t st) {
+  bool ok = true;
+  if (!(M.sparse && M.store != 0))
+    ok &= hipMemsetAsync(at<int32_t>(ws, Ly.colsync), 0, Ly.tail - Ly.colsync, st) == hipSuccess;
+  if (M.nc > 0)
+    ok &= hipMemsetAsync(at<double>(ws, Ly.tail) + tail_gran_offset_doubles(), 0,
+                         sizeof(double) * (tail_scratch_doubles() - tail_gran_offset_doubles()), st) == hipSuccess;
+  return ok;
+}
+
+// Upload a plan on the device's side stream and make `st` wait for it: the
+// copy runs while the first linearize kernel does instead of queueing behind
+// it. Callers have waited for every earlier launch on `st` (the prologue's
+// event or a stream sync), so nothing still running there reads `dst`.
+bool upload_plan(Staging *SG, PlanMeta &M, char *dst, hipStream_t st) {
+  if (!(M.sparse && !M.h_plan.empty())) return true;
+  const size_t nb = sizeof(int32_t) * M.h_plan.size();
+  if (SG->plan_pending && hipEventSynchronize(SG->plan_ev) != hipSuccess) return false;
+  SG->plan_pending = false;
+  if (!pinned_reserve(SG->plan_up, SG->plan_cap, nb)) return false;
+  memcpy(SG->plan_up, M.h_plan.data(), nb);
+  bool ok = hipMemcpyAsync(dst, SG->plan_up, nb, hipMemcpyHostToDevice, SG->side) == hipSuccess;
+  ok &= hipEventRecord(SG->plan_ev, SG->side) == hipSuccess;
+  ok &= hipStreamWaitEvent(st, SG->plan_ev, 0) == hipSuccess;
+  SG->plan_pending = ok;
+  return ok;
+}
+
+// Test hook for the bounded waits (tests/test_gpu_backend.py, knob
+// debug_drop_item): drop one item of sparse_llt_kernel's dispatch list, so the
+// items that read its blocks wait on a flag that is never set; the waits time
+// out and the iteration ends as a solve failure (dx = 0) instead of hanging.
+// On the chip-wide path (global factor) the item is dropped from
+// df_factor_kernel's dispatch list instead.
+void apply_drop_item(PlanMeta &M) {
+  const int d = drop_item_knob();
+  if (d < 0 || !M.sparse || M.h_plan.empty()) return;
+  if (M.store == 0 && M.n_dfitems > 0) {
+    int32_t *di = M.h_plan.data() + M.off_dfitems;
+    if (d < M.n_dfitems) {
+      for (int t = d; t + 1 < M.n_dfitems; t++) di[t] = di[t + 1];
+      M.n_dfitems -= 1;
+    }
+    return;
+  }
+  if (M.img.off_wave_ptr >= (int64_t)M.h_plan.size()) return;
+  int32_t *wp = M.h_plan.data() + M.img.off_wave_ptr, *wi = M.h_plan.data() + M.img.off_witems;
+  if (d < wp[1]) {
+    for (int t = d; t + 1 < wp[1]; t++) wi[t] = wi[t + 1];
+    wp[1] -= 1;
+  }
+}
+
+// The host prepare, per solve call (the reference's _unique / searchsorted
+// also synchronise): read ii/jj (+ K) once — the call's only host sync — rank the
+// ids, fetch the plan (or defer it to the first solve) and enqueue ONE
+// upload of everything the launches read (pinned staging, above).
+int gn_prepare_impl(const m3s_gn_args *a, hipStream_t st) {
+  const Layout Ly = gn_layout(a->N, a->HW, a->E);
+  void *ws = a->workspace;
+  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
+  Staging *SG = stage_for_device();
+  if (!SG) return M3S_ELAUNCH;
+  if (SG->pending && hipEventSynchronize(SG->ev) != hipSuccess) return M3S_ELAUNCH;
+  SG->pending = false;
+  const int64_t E = a->E;
+  if (!pinned_reserve(SG->down, SG->down_cap, 64 + 2 * sizeof(int64_t) * (size_t)E)) return M3S_ELAUNCH;
+  float *hK = reinterpret_cast<float *>(SG->down);  // calib intrinsics, read with ii/jj
+  int64_t *hii = reinterpret_cast<int64_t *>(SG->down + 64), *hjj = hii + E;
+  for (int q = 0; q < 9; q++) hK[q] = 0.f;
+  if (a->mode == M3S_MODE_CALIB &&
+      hipMemcpyAsync(hK, a->K, sizeof(float) * 9, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return M3S_ELAUNCH;
+  if (a->N > 1 && a->dx_out && hipMemsetAsync(a->dx_out, 0, sizeof(float) * 7 * (a->N - 1), st) != hipSuccess)
+    return M3S_ELAUNCH;
+  if (E > 0 && hipMemcpyAsync(hii, a->ii, sizeof(int64_t) * E, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return M3S_ELAUNCH;
+  if (E > 0 && hipMemcpyAsync(hjj, a->jj, sizeof(int64_t) * E, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return M3S_ELAUNCH;
+  if (hipStreamSynchronize(st) != hipSuccess) return M3S_ELAUNCH;
+  std::vector<int32_t> ri, rj;
+  const int nu = host_remap(hii, hjj, E, ri, rj);
+  const bool bad = nu > a->N;
+  const bool force_dense = force_dense_knob();
+  PlanMeta meta;
+  bool hit = false;
+  if (!bad && plan_cache_enabled()) {
+    std::lock_guard<std::mutex> g(g_cache_mu);
+    for (size_t q = 0; q < g_cache.size(); q++) {
+      const PlanCacheEntry &C = g_cache[q];
+      if (C.N == a->N && C.HW == a->HW && C.E == E && C.dense == force_dense &&
+          C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
+        meta = C.meta;
+        std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
+        hit = true;
+        break;
+      }
+    }
+  }
+  if (hit && E > 0 && meta.eorder.empty()) build_eorder(meta.rj, 0, E, meta.eorder);  // cached by the prologue path
+  if (!hit) {
+    // ranks and the full-range task table now (the first linearize needs
+    // them); the symbolic plan is built by the first solve of this call,
+    // while the first linearize kernel runs (finish_plan)
+    meta.h_ri = ri;
+    meta.rj = rj;
+    if (E > 0) build_eorder(meta.rj, 0, E, meta.eorder);
+    meta.sparse = !bad && !force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
+    meta.plan_pending = !bad && a->N > 1;
+    meta.force_dense = force_dense;
+  }
+  for (int q = 0; q < 8; q++) meta.h_info[q] = 0;
+  for (int q = 0; q < 64; q++) meta.h_flags[q] = 0;
+  meta.h_info[M3S_INFO_N_UNIQUE] = nu;
+  if (bad) meta.h_info[M3S_INFO_BAD_EDGE] = 1, meta.h_flags[kFlagStop] = 1;
+  if (a->mode == M3S_MODE_CALIB) {  // K row-major: fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]
+    meta.has_K = true;
+    meta.K4[0] = hK[0], meta.K4[1] = hK[4], meta.K4[2] = hK[2], meta.K4[3] = hK[5];
+  }
+  meta.planes_ok = false;
+  meta.range_b = 0, meta.range_e = E, meta.order_ok = E > 0;
+  if (meta.sparse && !meta.plan_pending && meta.lds_bytes > 64 * 1024) set_lds_attributes_once();
+  std::lock_guard<std::mutex> g(g_reg_mu);
+  PlanMeta &M = g_reg[ws];
+  M = std::move(meta);
+  bool ok = true;
+  if (!M.plan_pending) ok &= reset_plan_flags(M, Ly, ws, st);
+  M.epoch = 0;
+  if (!M.plan_pending) apply_drop_item(M);
+  // one upload: flags | rank_i | rank_j | edge counters | edge order [| plan] (the
+  // layout keeps them in this order), then info (the caller's tensor) from
+  // the same buffer
+  const bool with_plan = M.sparse && !M.plan_pending && !M.h_plan.empty();
+  const bool with_tasks = E > 0;
+  size_t n_up = with_plan ? Ly.plan - Ly.flags + sizeof(int32_t) * M.h_plan.size()
+                          : with_tasks ? Ly.eorder - Ly.flags + sizeof(int32_t) * M.eorder.size()
+                                       : Ly.edge_cnt - Ly.flags + edge_cnt_bytes(E);
+  n_up = align_up(n_up, 16);
+  if (!pinned_reserve(SG->up, SG->up_cap, n_up + sizeof M.h_info)) return M3S_ELAUNCH;
+  char *up = SG->up;
+  memcpy(up, M.h_flags, sizeof M.h_flags);
+  memset(up + (Ly.edge_cnt - Ly.flags), 0, edge_cnt_bytes(E));  // the fused finalize's counters
+  if (E > 0) {
+    memcpy(up + (Ly.rank_i - Ly.flags), M.h_ri.data(), sizeof(int32_t) * E);
+    memcpy(up + (Ly.rank_j - Ly.flags), M.rj.data(), sizeof(int32_t) * E);
+  }
+  if (with_tasks) memcpy(up + (Ly.eorder - Ly.flags), M.eorder.data(), sizeof(int32_t) * M.eorder.size());
+  if (with_plan) memcpy(up + (Ly.plan - Ly.flags), M.h_plan.data(), sizeof(int32_t) * M.h_plan.size());
+  memcpy(up + n_up, M.h_info, sizeof M.h_info);
+  ok &= hipMemcpyAsync(at<char>(ws, Ly.flags), up, n_up, hipMemcpyHostToDevice, st) == hipSuccess;
+  ok &= hipMemcpyAsync(a->info, up + n_up, sizeof M.h_info, hipMemcpyHostToDevice, st) == hipSuccess;
+  ok &= hipEventRecord(SG->ev, st) == hipSuccess;
+  SG->pending = ok;
+  return ok ? M3S_OK : M3S_ELAUNCH;
+}
+
+// The deferred half of a cold prepare: the symbolic plan (ordering, fill,
+// update lists; build_plan_meta) on the host, its upload, and the per-plan
+// flag resets. Called by a call's first solve, i.e. after its first
+// linearize is on the stream: the analysis runs while that kernel does.
+int finish_plan(const m3s_gn_args *a, const Layout &Ly, hipStream_t st) {
+  void *ws = a->workspace;
+  std::vector<int32_t> ri, rj;
+  bool force_dense;
+  {
+    std::lock_guard<std::mutex> g(g_reg_mu);
+    auto it = g_reg.find(ws);
+    if (it == g_reg.end()) return M3S_EINVAL;
+    if (!it->second.plan_pending) return M3S_OK;
+    ri = it->second.h_ri;
+    rj = it->second.rj;
+    force_dense = it->second.force_dense;
+  }
+  PlanMeta built = build_plan_meta(a, Ly, ri, rj, force_dense);
+  if (built.sparse && built.lds_bytes > 64 * 1024) set_lds_attributes_once();
+  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
+  Staging *SG = stage_for_device();
+  if (!SG) return M3S_ELAUNCH;
+  if (SG->plan_pending && hipEventSynchronize(SG->plan_ev) != hipSuccess) return M3S_ELAUNCH;
+  SG->plan_pending = false;
+  std::lock_guard<std::mutex> g(g_reg_mu);
+  PlanMeta &M = g_reg[ws];
+  M.sparse = built.sparse, M.store = built.store, M.asm_lds = built.asm_lds, M.lds_bytes = built.lds_bytes;
+  M.m = built.m, M.S = built.S, M.levels = built.levels, M.plan_len = built.plan_len;
+  M.n_items = built.n_items, M.n_tasks = built.n_tasks, M.n_parts = built.n_parts, M.nc = built.nc;
+  M.off_dfitems = built.off_dfitems, M.n_dfitems = built.n_dfitems, M.nnz = built.nnz;
+  M.n_dfsparse = built.n_dfsparse;
+  M.img = built.img;
+  M.h_plan = std::move(built.h_plan);
+  M.plan_pending = false;
+  if (plan_cache_enabled()) {
+    PlanCacheEntry C;
+    C.N = a->N, C.HW = a->HW, C.E = a->E, C.dense = force_dense, C.ri = ri, C.rj = rj;
+    C.tail_min = dense_tail_min();
+    C.meta = M;
+    std::lock_guard<std::mutex> gc(g_cache_mu);
+    g_cache.insert(g_cache.begin(), std::move(C));
+    if (g_cache.size() > kPlanCacheSize) g_cache.pop_back();
+  }
+  bool ok = reset_plan_flags(M, Ly, ws, st);
+  apply_drop_item(M);
+  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
+  return ok ? M3S_OK : M3S_ELAUNCH;
+}
+
+// The host half of an async prepare (gn_prepare_async), at the first point a
+// call needs its ids on the host (its first solve, or a sharded rank's edge
+// range): wait for the prologue (normally long done: the first linearize is
+// queued behind it), read ii / jj / K from the pinned slot, rank the ids on
+// the host (the plan and its cache key need them), and fetch the cached plan;
+// a miss leaves the plan to finish_plan. The linearize state of the entry
+// (range, task table, planes) is the prologue's and stays.
+int host_finish(const m3s_gn_args *a, hipStream_t st) {
+  void *ws = a->workspace;
+  int slot = -1;
+  {
+    std::lock_guard<std::mutex> g(g_reg_mu);
+    auto it = g_reg.find(ws);
+    if (it == g_reg.end()) return M3S_EINVAL;
+    if (!it->second.host_pending) return M3S_OK;
+    slot = it->second.slot;
+  }
+  const int64_t E = a->E;
+  std::vector<int64_t> hii((size_t)E), hjj((size_t)E);
+  float hK[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  {
+    std::lock_guard<std::mutex> stage_lock(g_stage_mu);
+    Staging *SG = stage_for_device();
+    if (!SG || slot < 0 || slot >= (int)SG->slots.size()) return M3S_ELAUNCH;
+    DownSlot &D = SG->slots[slot];
+    if (hipEventSynchronize(D.ev) != hipSuccess) return M3S_ELAUNCH;
+    if (a->mode == M3S_MODE_CALIB) memcpy(hK, D.p, sizeof hK);
+    if (E > 0) {
+      memcpy(hii.data(), D.p + 64, sizeof(int64_t) * (size_t)E);
+      memcpy(hjj.data(), D.p + 64 + sizeof(int64_t) * (size_t)E, sizeof(int64_t) * (size_t)E);
+    }
+    D.busy = false;
+  }
+  std::vector<int32_t> ri, rj;
+  const int nu = host_remap(hii.data(), hjj.data(), E, ri, rj);
+  const bool bad = nu > a->N;  // the prologue has stopped the call (flags, info)
+  const Layout Ly = gn_layout(a->N, a->HW, a->E);
+  bool force_dense;
+  {
+    std::lock_guard<std::mutex> g(g_reg_mu);
+    force_dense = g_reg.at(ws).force_dense;
+  }
+  PlanMeta hitm;
+  bool hit = false;
+  if (!bad && plan_cache_enabled()) {
+    std::lock_guard<std::mutex> g(g_cache_mu);
+    for (size_t q = 0; q < g_cache.size(); q++) {
+      const PlanCacheEntry &C = g_cache[q];
+      if (C.N == a->N && C.HW == a->HW && C.E == E && C.dense == force_dense &&
+          C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
+        hitm = C.meta;
+        std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
+        hit = true;
+        break;
+      }
+    }
+  }
+  if (hit && hitm.sparse && hitm.lds_bytes > 64 * 1024) set_lds_attributes_once();
+  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
+  Staging *SG = stage_for_device();
+  if (!SG) return M3S_ELAUNCH;
+  std::lock_guard<std::mutex> g(g_reg_mu);
+  PlanMeta &M = g_reg[ws];
+  M.host_pending = false, M.slot = -1;
+  M.h_ri = std::move(ri), M.rj = std::move(rj);
+  M.K4[0] = hK[0], M.K4[1] = hK[4], M.K4[2] = hK[2], M.K4[3] = hK[5];
+  if (bad) {
+    M.sparse = false, M.plan_pending = false;
+    return M3S_OK;
+  }
+  if (!hit) return M3S_OK;  // plan_pending: finish_plan builds it
+  M.sparse = hitm.sparse, M.store = hitm.store, M.asm_lds = hitm.asm_lds, M.lds_bytes = hitm.lds_bytes;
+  M.m = hitm.m, M.S = hitm.S, M.levels = hitm.levels, M.plan_len = hitm.plan_len;
+  M.n_items = hitm.n_items, M.n_tasks = hitm.n_tasks, M.n_parts = hitm.n_parts, M.nc = hitm.nc;
+  M.off_dfitems = hitm.off_dfitems, M.n_dfitems = hitm.n_dfitems, M.nnz = hitm.nnz;
+  M.n_dfsparse = hitm.n_dfsparse;
+  M.img = hitm.img;
+  M.h_plan = std::move(hitm.h_plan);
+  M.plan_pending = false;
+  bool ok = reset_plan_flags(M, Ly, ws, st);
+  apply_drop_item(M);
+  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
+  return ok ? M3S_OK : M3S_ELAUNCH;
+}
+
+// Prepare a call without a host round trip: one prologue kernel on the stream
+// (ranks, task table, flags, info, dx_out; the ids to pinned memory) and the
+// registry entry; the host reads the ids later (host_finish), while the first
+// linearize runs. Large edge sets (> kProMaxE) take the synchronous prepare.
+int gn_prepare_async(const m3s_gn_args *a, hipStream_t st) {
+  const int64_t E = a->E;
+  if (E > kProMaxE || a->N > (int64_t)1 << 30 || knob<K_prologue>() == 0) return gn_prepare_impl(a, st);
+  const Layout Ly = gn_layout(a->N, a->HW, E);
+  void *ws = a->workspace;
+  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
+  Staging *SG = stage_for_device();
+  if (!SG) return M3S_ELAUNCH;
+  const int slot = acquire_slot(*SG, 64 + 2 * sizeof(int64_t) * (size_t)E);
+  if (slot < 0) return M3S_ELAUNCH;
+  DownSlot &D = SG->slots[slot];
+  ProArgs P;
+  P.ii = a->ii, P.jj = a->jj;
+  P.K = a->mode == M3S_MODE_CALIB ? a->K : nullptr;
+  P.down_K = reinterpret_cast<float *>(D.dp);
+  P.down_ii = reinterpret_cast<int64_t *>(D.dp + 64);
+  P.down_jj = P.down_ii + E;
+  P.E = (int)E, P.N = (int)a->N, P.P2 = prologue_p2(E);
+  P.flags = at<int32_t>(ws, Ly.flags), P.rank_i = at<int32_t>(ws, Ly.rank_i), P.rank_j = at<int32_t>(ws, Ly.rank_j);
+  P.eorder = at<int32_t>(ws, Ly.eorder), P.info = a->info, P.edge_cnt = at<uint32_t>(ws, Ly.edge_cnt);
+  P.dx_out = a->dx_out;
+  P.n_dx = (a->N > 1 && a->dx_out) ? (int)(7 * (a->N - 1)) : 0;
+  const size_t lds = prologue_lds(P.E, P.P2);
+  if (lds > 64 * 1024) set_lds_attributes_once();
+  gn_prologue_kernel<<<1, kProThreads, lds, st>>>(P);
+  if (launch_ok() != M3S_OK || hipEventRecord(D.ev, st) != hipSuccess) {
+    D.busy = false;
+    return M3S_ELAUNCH;
+  }
+  PlanMeta meta;
+  meta.host_pending = true, meta.slot = slot;
+  meta.has_K = a->mode == M3S_MODE_CALIB;
+  meta.force_dense = force_dense_knob();
+  meta.sparse = !meta.force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
+  meta.plan_pending = a->N > 1;
+  meta.range_b = 0, meta.range_e = E, meta.order_ok = E > 0;
+  std::lock_guard<std::mutex> g(g_reg_mu);
+  PlanMeta &M = g_reg[ws];
+  if (M.host_pending && M.slot >= 0 && M.slot < (int)SG->slots.size() && M.slot != slot)
+    SG->slots[M.slot].busy = false;  // a re-prepare of a workspace whose ids were never read
+  M = std::move(meta);
+  M.epoch = 0;
+  return M3S_OK;
+}

@@ -4,8 +4,6 @@
 // iteration in one launch, or one linearize_kernel<MODE, TRACK> launch per
 // iteration whose last chunk runs track_solve_block. track_impl launches them.
 
-namespace {
-
 // --------------------------------------------------------------- tracker --
 
 constexpr size_t kTrackStateOff = 0;
@@ -539,5 +537,3 @@ int track_impl(const m3s_track_args *a, int mode, void *stream) {
   }
   return M3S_OK;
 }
-
-}  // namespace

@@ -3,8 +3,6 @@
 // (track_prep_clear_kernel, track_prep_kernel, track_prep_count_kernel) and
 // track_frame_impl, which then runs track_impl (gn/track.h) on the prepared rows.
 
-namespace {
-
 // ------------------------------------------------------ track_frame prep --
 // The front end of FrameTracker.track (tracker.py:41-67, 103-108, 129-154)
 // ahead of the tracker launches above: three small launches per call.
@@ -193,5 +191,3 @@ int track_frame_impl(const m3s_track_frame_args *a, void *stream) {
   t.workspace_bytes = Ly.map;
   return track_impl(&t, calib ? M3S_MODE_CALIB : M3S_MODE_RAYS, stream);
 }
-
-}  // namespace

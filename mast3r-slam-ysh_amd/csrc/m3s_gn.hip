@@ -1,25 +1,28 @@
 // m3s_gn.hip — MI355X (gfx950) Gauss-Newton backend and tracker for MASt3R-SLAM.
 //
-// One translation unit: the backend below, section by section, then the
-// tracker (gn/track.h) and the track_frame front end (gn/track_frame.h), then
-// the two debug kernels and the C exports. The gn/*.h files are parts of this
-// file, not stand-alone headers: each reopens the anonymous namespace and
-// relies on what stands before it. Every launch is on the caller's stream; a
-// call does not wait for the device except where noted. Sections are named by
-// their rule lines (`// ---- name --`).
+// One translation unit: the backend's device code below, section by section,
+// then the host side of the backend (gn/knobs.h, gn/launch.h, gn/plan.h,
+// gn/iterate.h), the tracker (gn/track.h) and the track_frame front end
+// (gn/track_frame.h), then the two debug kernels and the C exports. The gn/*.h
+// files are parts of this file, not stand-alone headers: each is text inside
+// the one anonymous namespace opened below, has no includes or guards of its
+// own, and relies on what stands before it. Every launch is on the caller's
+// stream; a call does not wait for the device except where noted. Sections of
+// this file are named by their rule lines (`// ---- name --`).
 //
-// gauss_newton_{points,rays,calib} (gn_full, section host):
+// gauss_newton_{points,rays,calib} (gn_full, gn/iterate.h):
 //   prepare    gn_prologue_kernel (call prologue): ranks the edge ids, writes the
 //              linearize edge order, flags, info, dx; the ids go to pinned memory
 //              and the host builds (or fetches from the plan cache) the symbolic
-//              plan while the first linearize runs. Above 2048 edges: the host
-//              prepare (one stream sync, gn_prepare_impl).
-//   iteration  1 linearize launch; its last chunk of an edge finalizes the edge:
+//              plan while the first linearize runs (gn/plan.h). Above 2048
+//              edges: the host prepare (one stream sync, gn_prepare_impl).
+//   iteration  1 linearize launch (gn/launch.h); its last chunk of an edge
+//              finalizes the edge:
 //                first iteration   linearize_gather_kernel (pipelined gathering
 //                                  launch), or linearize_kernel (linearize)
 //                                  where the gathering kernel does not apply
 //                later iterations  linearize_packed_kernel (linearize)
-//              then the solve (gn_solve_impl), by the plan:
+//              then the solve (gn_solve_impl, gn/iterate.h), by the plan:
 //                factor fits the LDS (small graphs): sparse_llt_kernel<1> / <2>,
 //                  one workgroup: assembly, LLT, back-substitution, retraction,
 //                  stop flag (block-sparse LLT; assemble_slots_kernel first when
@@ -28,9 +31,10 @@
 //                  assemble_slots_kernel (block-sparse LLT),
 //                  df_factor_kernel (wave-level dataflow factorisation),
 //                  tail_pair_kernel when the plan has a dense tail (under the
-//                  bare rule behind the dense tail sections, "Round 5"; from 32
-//                  tail columns its extra workgroups run the sparse back-
-//                  substitution, gcol_worker), else col_backsub_kernel (dataflow)
+//                  bare rule inside the section "dense tail over many
+//                  workgroups", "Round 5"; from 32 tail columns its extra
+//                  workgroups run the sparse back-substitution, gcol_worker),
+//                  else col_backsub_kernel (dataflow)
 //                else: sparse_llt_kernel<0>, in two phases around border_kernel
 //                  (border kernel) and tail_llt_kernel (dense tail on the f64
 //                  MFMA) with a dense tail
@@ -45,12 +49,15 @@
 // track_frame (track_frame_impl, gn/track_frame.h): track_prep_clear_kernel,
 //   track_prep_kernel, track_prep_count_kernel, then the tracker's launches.
 // The test build (-DM3S_TEST_PATHS) adds the A/B reference paths behind the
-// test-only knobs (host): col_factor_kernel (column tasks), chol_small_kernel
-// (small dense Cholesky), tail_cyc_kernel, the VGPR-staged gathering kernel.
+// test-only knobs (gn/knobs.h): col_factor_kernel (column tasks),
+// chol_small_kernel (small dense Cholesky), tail_cyc_kernel, the VGPR-staged
+// gathering kernel.
 //
-// Order rule: device functions and kernels keep their relative order, and so
-// does the order in which host code first names each kernel template (that
-// decides where its instantiation lands). The code object holds real calls to
+// Order rule: the sections below and then the include list are the order of
+// the device code. Device functions and kernels keep their relative order, in
+// this file and inside a part, and the first host mention of each kernel
+// template keeps its place (gn/launch.h, gn/plan.h, gn/iterate.h; it decides
+// where the instantiation lands). The code object holds real calls to
 // non-inlined device functions, so a reordering changes pc-relative literals
 // and the device code can no longer be compared instruction for instruction
 // with the build before (tools/code_identity.py). Host code may move otherwise.
@@ -4873,1309 +4880,12 @@ int check_args(const m3s_gn_args *a) {
   return M3S_OK;
 }
 
-// Solver knobs: the measured-best defaults, overridable per process by the
-// environment (read ONCE, at the first use) and at run time by m3s_set_knob
-// (bench legs and tests that A/B a path in one process). Each knob is declared
-// once, as a row of one of the two lists below: the values (Knobs), the
-// environment read, set_knob's lookup and its plan-cache drop, and the product
-// build's constants are all derived from the row.
-//   X(name, environment variable or nullptr, default, shapes a plan)
-// The product library carries the knobs of its own paths only; the A/B
-// reference paths (column-task factor, one-workgroup tail, forced dense /
-// one-workgroup solves) and the bounded-wait test hook exist in the test
-// build (-DM3S_TEST_PATHS: libm3s_gn_test.so, tests/conftest.py `test_lib`),
-// and in the product build a test-only knob is its default as a compile-time
-// constant, so no A/B branch reaches the product.
-// Knobs that shape a plan (its schedule, split lists, tail, path) are not all
-// in the plan-cache key: a change drops every cached plan (set_knob), so no
-// launch reads a plan built for another path (e.g. a chip-path plan, cached
-// unscheduled, on the one-workgroup kernel).
-#define M3S_PRODUCT_KNOBS(X)                                                                                           \
-  X(plan_cache, "M3S_PLAN_CACHE", 1, false)   /* 0 = symbolic analysis every call (cold calls, bench.py) */            \
-  X(dense_tail_min, "M3S_DENSE_TAIL_MIN", kDenseTailMin, true) /* smallest top clique solved dense (0: never) */       \
-  X(track_persistent, "M3S_TRACK_PERSISTENT", 1, false) /* 0 = one tracker launch per iteration */                     \
-  X(prologue, "M3S_PROLOGUE", 1, false)       /* 0 = host prepare (ids read back, then the uploads) */
-#define M3S_TEST_KNOBS(X)                                                                                              \
-  X(dense, "M3S_DENSE", 0, true)              /* 1 = dense fallback LLT (only the value 1 counts) */                   \
-  X(cols, "M3S_COLS", 1, true)                /* 0 = large graphs on sparse_llt_kernel's one workgroup */              \
-  X(df, "M3S_DF", 1, true)                    /* 0 = column tasks + border_kernel instead of the dataflow */           \
-  X(tail_cyc, "M3S_TAIL_CYC", 1, true)        /* 0 = the dense tail on one workgroup */                                \
-  X(tail_mfma, "M3S_TAIL_MFMA", 1, true)      /* 0 = the dense tail in sparse_llt_kernel */                            \
-  X(border_split, "M3S_BORDER_SPLIT", 1, true) /* 0 = tail border in the one-workgroup kernel */                       \
-  X(debug_drop_item, nullptr, -1, true)       /* drop one LLT dispatch item (bounded-wait test) */                     \
-  X(gather_lds, nullptr, 1, false)            /* 0 = the round-2 VGPR-staged gathering kernel (bitwise reference) */   \
-  X(tail_pair, "M3S_TAIL_PAIR", 1, false)     /* 0 = tail_cyc_kernel (one tile column per workgroup) */                \
-  X(tail_warm, "M3S_TAIL_WARM", 1, false)     /* 0 = no warm-up of the tail's diagonal factor code */                  \
-  X(gcomb, "M3S_GCOMB", 1, false)             /* 0 = col_backsub_kernel after the tail, not gcol_worker */             \
-  X(gcomb_wg, "M3S_GCOMB_WG", 64, false)      /* gcol_worker workgroups, >= 1 (64 measured best at 128 / 256 KFs) */   \
-  /* the workers pay off once the dense tail's chain is long enough to hide the X_k recursion: 256 KFs                 \
-     (42-column tail) 0.751 -> 0.712 ms per 3-iteration call, 128 KFs (a shorter tail) 0.493 -> 0.501                  \
-     (profiles/r05/solve_ab_gcomb_rotated.txt) */                                                                      \
-  X(gcomb_min_nc, "M3S_GCOMB_MIN_NC", 32, false) /* smallest dense tail (block columns) that takes the workers */
-
-#define M3S_KNOB_ID(name, env, def, shaping) K_##name,
-#define M3S_KNOB_DEF(name, env, def, shaping) {K_##name, #name, env, def, shaping},
-#define M3S_KNOB_DEFAULT(name, env, def, shaping) \
-  case K_##name: return def;
-enum KnobId : int { M3S_PRODUCT_KNOBS(M3S_KNOB_ID) M3S_TEST_KNOBS(M3S_KNOB_ID) };  // = the row's index in kKnobDefs
-struct KnobDef {
-  KnobId id;
-  const char *name, *env;
-  int def;
-  bool shaping;
-};
-constexpr KnobDef kKnobDefs[] = {  // the knobs this build knows by name
-    M3S_PRODUCT_KNOBS(M3S_KNOB_DEF)
-#ifdef M3S_TEST_PATHS
-    M3S_TEST_KNOBS(M3S_KNOB_DEF)
-#endif
-};
-constexpr int kNumKnobs = (int)(sizeof(kKnobDefs) / sizeof(kKnobDefs[0]));
-constexpr bool knob_rows_in_id_order() {
-  for (int k = 0; k < kNumKnobs; k++)
-    if (kKnobDefs[k].id != k) return false;
-  return true;
-}
-static_assert(knob_rows_in_id_order(), "Knobs::v is indexed by KnobId: row k of kKnobDefs is knob k");
-constexpr int knob_default(KnobId k) {
-  switch (k) {
-    M3S_PRODUCT_KNOBS(M3S_KNOB_DEFAULT)
-    M3S_TEST_KNOBS(M3S_KNOB_DEFAULT)
-    default: return 0;
-  }
-}
-#undef M3S_KNOB_ID
-#undef M3S_KNOB_DEF
-#undef M3S_KNOB_DEFAULT
-
-struct Knobs {
-  std::atomic<int> v[kNumKnobs];
-  Knobs() {
-    for (int k = 0; k < kNumKnobs; k++) {
-      v[k] = kKnobDefs[k].def;
-      if (kKnobDefs[k].env)
-        if (const char *e = std::getenv(kKnobDefs[k].env)) v[k] = std::atoi(e);
-    }
-  }
-};
-Knobs &knobs() {
-  static Knobs k;  // thread-safe one-time initialisation
-  return k;
-}
-// A knob's value: the run-time one where this build has the knob, else (a
-// test-only knob in the product build) its default, a compile-time constant.
-template <KnobId K>
-constexpr int knob() {
-  if constexpr (K < kNumKnobs)
-    return knobs().v[K];
-  else
-    return knob_default(K);
-}
-#ifdef M3S_TEST_PATHS
-#define M3S_TEST_KNOB inline
-#else
-#define M3S_TEST_KNOB constexpr
-#endif
-M3S_TEST_KNOB bool cols_path() { return knob<K_cols>() != 0; }
-M3S_TEST_KNOB bool df_path() { return knob<K_df>() != 0; }
-M3S_TEST_KNOB bool tail_cyc() { return knob<K_tail_cyc>() != 0; }
-M3S_TEST_KNOB bool tail_mfma() { return knob<K_tail_mfma>() != 0; }
-M3S_TEST_KNOB bool border_split() { return knob<K_border_split>() != 0; }
-M3S_TEST_KNOB bool force_dense_knob() { return knob<K_dense>() == 1; }
-M3S_TEST_KNOB int drop_item_knob() { return knob<K_debug_drop_item>(); }
-M3S_TEST_KNOB bool gather_lds_path() { return knob<K_gather_lds>() != 0; }
-M3S_TEST_KNOB bool tail_pair_path() { return knob<K_tail_pair>() != 0; }
-M3S_TEST_KNOB bool tail_warm_knob() { return knob<K_tail_warm>() != 0; }
-M3S_TEST_KNOB bool gcomb_knob() { return knob<K_gcomb>() != 0; }
-M3S_TEST_KNOB int gcomb_wg_knob() { return std::max(1, knob<K_gcomb_wg>()); }
-M3S_TEST_KNOB int gcomb_min_nc_knob() { return knob<K_gcomb_min_nc>(); }
-#undef M3S_TEST_KNOB
-#ifndef M3S_TEST_PATHS
-static_assert(cols_path() && df_path() && !force_dense_knob() && gcomb_wg_knob() == 64,
-              "product build: the test-only knobs are constants");
-#endif
-inline int dense_tail_min() { return knob<K_dense_tail_min>(); }
-inline bool plan_cache_enabled() { return knob<K_plan_cache>() != 0; }
-
-// In-call timing (m3s_debug_call_timing): the drop-in call sets a start /
-// stop event pair for its next linearize launch, which then goes through
-// hipExtLaunchKernel: the events take the dispatch's own begin / end
-// timestamps (the kernel's span, as a kernel trace records it; events
-// recorded around the launch read 8-12% more, profiles/r04/prof_split_*.txt)
-// {start, stop}; thread_local: set and consumed by one gn_full call on its own
-// thread (a call on another thread without timing never sees it). launch_lin
-// clears it when it used the pair, so the caller can tell a span whose
-// linearize went through another launch (the pack == 0 path) and fall back to
-// the events recorded around it.
-thread_local hipEvent_t *g_lin_ext_ev = nullptr;
-// the same for the one-workgroup solve's launch (sparse_llt_kernel, small
-// graphs: the whole solve of an iteration is that one dispatch)
-thread_local hipEvent_t *g_slv_ext_ev = nullptr;
-template <typename K>
-void launch_lin(K kernel, dim3 g, dim3 b, hipStream_t st, const LinArgs &L) {
-  if (g_lin_ext_ev) {
-    hipExtLaunchKernelGGL(kernel, g, b, 0, st, g_lin_ext_ev[0], g_lin_ext_ev[1], 0, L);
-    g_lin_ext_ev = nullptr;
-  } else {
-    kernel<<<g, b, 0, st>>>(L);
-  }
-}
-
-// pack: 0 gathering kernel, 1 gathering kernel that stores the planes,
-// 2 packed kernel (reads the planes; VEC layout only)
-template <int MODE, bool TRACK>
-int launch_linearize(const LinArgs &L, int64_t blocks, bool vec, int pack, hipStream_t st) {
-  if (blocks <= 0) return M3S_OK;
-  const dim3 g((unsigned)blocks), b(kThreads);
-  if (TRACK || pack == 0) {
-    if (vec)
-      linearize_kernel<MODE, TRACK, true, false><<<g, b, 0, st>>>(L);
-    else
-      linearize_kernel<MODE, TRACK, false, false><<<g, b, 0, st>>>(L);
-  } else if (pack == 1) {
-    if (vec && gather_lds_path() && L.HW <= (int64_t(1) << 24))  // (24-bit index products)
-      launch_lin(linearize_gather_kernel<MODE>, g, b, st, L);
-    else if (vec)
-      launch_lin(linearize_kernel<MODE, false, true, true>, g, b, st, L);
-    else
-      launch_lin(linearize_kernel<MODE, false, false, true>, g, b, st, L);
-  } else {
-    launch_lin(linearize_packed_kernel<MODE>, g, b, st, L);
-  }
-  return launch_ok();
-}
-
-template <bool TRACK>
-int dispatch_linearize(int mode, const LinArgs &L, int64_t blocks, bool vec, int pack, hipStream_t st) {
-  switch (mode) {
-    case M3S_MODE_POINTS: return launch_linearize<M3S_MODE_POINTS, TRACK>(L, blocks, vec, pack, st);
-    case M3S_MODE_RAYS: return launch_linearize<M3S_MODE_RAYS, TRACK>(L, blocks, vec, pack, st);
-    case M3S_MODE_CALIB: return launch_linearize<M3S_MODE_CALIB, TRACK>(L, blocks, vec, pack, st);
-  }
-  return M3S_EINVAL;
-}
-
-bool vec_ok(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
-// K is a device pointer; read it once per call (tiny D2H copy, not on the
-// iteration path). For graph capture the caller can pass params instead.
-int read_K(const float *K, ResidualParams &P, hipStream_t st) {
-  float k[9];
-  if (hipMemcpyAsync(k, K, sizeof k, hipMemcpyDeviceToHost, st) != hipSuccess) return M3S_ELAUNCH;
-  if (hipStreamSynchronize(st) != hipSuccess) return M3S_ELAUNCH;
-  P.fx = k[0], P.fy = k[4], P.cx = k[2], P.cy = k[5];
-  return M3S_OK;
-}
-
-struct PlanMeta {
-  int epoch = 0;  // solve launches since m3s_gn_prepare (column-task flags / tickets)
-  bool sparse = false;
-  int store = 0;  // sparse_llt_kernel<STORE>
-  bool asm_lds = false;  // LDS factor with room for the staged fin blocks: assembly in the LLT kernel
-  size_t lds_bytes = 0;
-  int m = 0, S = 0, levels = 0, plan_len = 0, n_items = 0, n_tasks = 0, n_parts = 0, nc = 0;
-  int nnz = 0;  // off-diagonal blocks (col_ptr[m])
-  int off_dfitems = 0, n_dfitems = 0;  // df_factor_kernel dispatch list (appended to the plan image)
-  int n_dfsparse = 0;                  // its sparse-column items (the border items follow)
-  PlanImage img;  // offsets (data vector cleared after upload)
-  // linearize state of this solve call: edge ranks, the task table of the
-  // edge range last linearized (host copy stays alive for the async upload)
-  // and whether that range's planes are stored
-  std::vector<int32_t> rj, h_ri;   // edge ranks (host copies of the uploaded arrays)
-  std::vector<int32_t> h_plan;     // flattened plan (host copy of the upload)
-  int32_t h_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int32_t h_flags[64] = {0};
-  bool has_K = false;
-  float K4[4] = {0.f, 0.f, 0.f, 0.f};  // fx, fy, cx, cy (calib; read once per call)
-  int64_t range_b = -1, range_e = -1;  // the edge range last linearized
-  bool order_ok = false;               // its edge order is in the workspace (Layout::eorder)
-  bool planes_ok = false;
-  // stepwise linearize with fused edge sums: edge_cnt arrivals counted since
-  // the counters were last zeroed (valid for every edge of the range); false:
-  // the counters hold arrivals of another range or of a drop-in call
-  uint32_t cnt_arr = 0;
-  bool cnt_ok = true;
-  std::vector<int32_t> eorder;         // host copy of the full range's order (host prepare)
-  // the symbolic plan of this call is built by its first solve (cache miss at
-  // prepare): the host analysis then overlaps the first linearize kernel
-  bool plan_pending = false;
-  bool force_dense = false;
-  // the ids of this call are still on their way to the host (device prologue,
-  // gn_prepare_async): host_finish reads them from pinned slot `slot`
-  bool host_pending = false;
-  int slot = -1;
-};
-
-// What a solve launch reads of the registry entry: the scalars and plan
-// offsets, not the host vectors (ranks, task tables, plan image) that the
-// entry keeps alive for queued uploads.
-PlanMeta solve_view(const PlanMeta &M) {
-  PlanMeta v;
-  v.epoch = M.epoch, v.sparse = M.sparse, v.store = M.store, v.asm_lds = M.asm_lds, v.lds_bytes = M.lds_bytes;
-  v.m = M.m, v.S = M.S, v.levels = M.levels, v.plan_len = M.plan_len, v.n_items = M.n_items;
-  v.n_tasks = M.n_tasks, v.n_parts = M.n_parts, v.nc = M.nc, v.off_dfitems = M.off_dfitems;
-  v.n_dfitems = M.n_dfitems;
-  v.n_dfsparse = M.n_dfsparse;
-  v.nnz = M.nnz;
-  v.img = M.img;  // offsets (its data vector is empty in the registry)
-  v.plan_pending = M.plan_pending;
-  return v;
-}
-// Host registry of the per-call plan (keyed by workspace): the stepwise API
-// calls prepare and solve separately.
-std::mutex g_reg_mu;
-std::unordered_map<const void *, PlanMeta> g_reg;
-
-// Pinned host staging of the per-call transfers (gn_prepare_impl: the D2H
-// reads of K, ii, jj and ONE H2D upload of flags | ranks | task table | plan;
-// finish_plan: a deferred plan; gn_linearize_impl: a sharded rank's task
-// table). Pageable copies were one staged, host-synchronous transfer each
-// (~7 per call); an event per buffer guards it until the copy that reads it
-// has left. The registry entries own no memory a queued copy still reads.
-// Pinned slot the device prologue writes a call's ii, jj and K into (host-
-// mapped); busy from the prepare until the host has read it (host_finish or
-// release), its event marks the prologue's completion.
-struct DownSlot {
-  char *p = nullptr, *dp = nullptr;  // host / device view
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool busy = false, used = false;
-};
-struct Staging {
-  char *down = nullptr, *up = nullptr, *plan_up = nullptr, *tasks_up = nullptr;
-  size_t down_cap = 0, up_cap = 0, plan_cap = 0, tasks_cap = 0;
-  hipEvent_t ev = nullptr, plan_ev = nullptr, tasks_ev = nullptr;
-  bool pending = false, plan_pending = false, tasks_pending = false;
-  hipStream_t side = nullptr;  // plan uploads that must not queue behind a running linearize
-  std::vector<DownSlot> slots;
-};
-// One staging set per device: an event recorded on one device's stream cannot
-// guard another device's copies (a process may drive GN on several GPUs).
-std::mutex g_stage_mu;
-std::unordered_map<int, Staging> g_stages;
-bool pinned_reserve(char *&p, size_t &cap, size_t need) {
-  if (need <= cap) return true;
-  if (p) (void)hipHostFree(p);
-  p = nullptr, cap = 0;
-  const size_t n = std::max<size_t>(need + need / 2, 1 << 16);
-  if (hipHostMalloc(reinterpret_cast<void **>(&p), n, hipHostMallocDefault) != hipSuccess) return false;
-  cap = n;
-  return true;
-}
-Staging *stage_for_device() {  // caller holds g_stage_mu
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  Staging &S = g_stages[dev];
-  for (hipEvent_t *e : {&S.ev, &S.plan_ev, &S.tasks_ev})
-    if (!*e && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return nullptr;
-  if (!S.side && hipStreamCreateWithFlags(&S.side, hipStreamNonBlocking) != hipSuccess) return nullptr;
-  return &S;
-}
-// A free pinned slot of at least `need` bytes (caller holds g_stage_mu).
-int acquire_slot(Staging &SG, size_t need) {
-  int k = -1;
-  for (int q = 0; q < (int)SG.slots.size(); q++)
-    if (!SG.slots[q].busy) {
-      k = q;
-      break;
-    }
-  if (k < 0) {
-    SG.slots.emplace_back();
-    k = (int)SG.slots.size() - 1;
-  }
-  DownSlot &D = SG.slots[k];
-  if (D.used && hipEventSynchronize(D.ev) != hipSuccess) return -1;  // its last prologue has finished writing
-  if (!D.ev && hipEventCreateWithFlags(&D.ev, hipEventDisableTiming) != hipSuccess) return -1;
-  if (need > D.cap) {
-    if (D.p) (void)hipHostFree(D.p);
-    D.p = D.dp = nullptr, D.cap = 0;
-    const size_t n = std::max<size_t>(need + need / 2, 1 << 16);
-    if (hipHostMalloc(reinterpret_cast<void **>(&D.p), n, hipHostMallocDefault) != hipSuccess) return -1;
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, D.p, 0) != hipSuccess) return -1;
-    D.dp = static_cast<char *>(dp), D.cap = n;
-  }
-  D.busy = true, D.used = true;
-  return k;
-}
-
-// Linearize edge order of an edge range: its edges (local indices) sorted by
-// KF j (block_task deals the (chunk, KF j)-sorted tasks over the XCDs).
-void build_eorder(const std::vector<int32_t> &rj, int64_t eb, int64_t E_loc, std::vector<int32_t> &out) {
-  out.resize((size_t)E_loc);
-  for (int64_t e = 0; e < E_loc; e++) out[e] = (int32_t)e;
-  std::stable_sort(out.begin(), out.end(), [&](int32_t x, int32_t y) { return rj[eb + x] < rj[eb + y]; });
-}
-
-constexpr size_t kMaxLdsBytes = 150 * 1024;
-// Defined behind gn_solve_impl: its body names the sparse_llt_kernel
-// specialisations, and where a kernel template is first named decides its
-// place in the device code (the order rule, m3s_gn.hip).
-void set_lds_attributes_once();
-
-// Host symbolic plans of recent edge sets (the same factor graph is usually
-// solved many times: every keyframe's local/global optimisation, every bench
-// step). Keyed by (N, HW, E, dense override, remapped ranks).
-struct PlanCacheEntry {
-  int64_t N = 0, HW = 0, E = 0;
-  bool dense = false;
-  int tail_min = 0;  // dense_tail_min() the plan was built with
-  std::vector<int32_t> ri, rj;
-  PlanMeta meta;
-};
-std::mutex g_cache_mu;
-std::vector<PlanCacheEntry> g_cache;  // most recent first
-constexpr size_t kPlanCacheSize = 4;
-
-// m3s_set_knob: the previous value, or -(1 << 30) for a name this build does
-// not know. A plan-shaping knob set to a different value drops the plan cache.
-int set_knob(const char *name, int value) {
-  Knobs &K = knobs();
-  for (int k = 0; k < kNumKnobs; k++)
-    if (std::strcmp(kKnobDefs[k].name, name) == 0) {
-      const int old = K.v[k].exchange(value);
-      if (kKnobDefs[k].shaping && old != value) {
-        std::lock_guard<std::mutex> g(g_cache_mu);
-        g_cache.clear();
-      }
-      return old;
-    }
-  return -(1 << 30);
-}
-
-// Symbolic plan + LDS budget + full-range task table for remapped ranks.
-PlanMeta build_plan_meta(const m3s_gn_args *a, const Layout &Ly, const std::vector<int32_t> &ri,
-                         const std::vector<int32_t> &rj, bool force_dense) {
-  PlanMeta meta;
-  const int64_t E = a->E;
-  if (a->N > 1) {
-    SparsePlan P;
-    // The dispatch schedule (witems) and the split update lists (PART items)
-    // serve only the one-workgroup sparse_llt_kernel; a factor in global
-    // memory on the chip-wide path (df_factor / tail / column back-
-    // substitution) needs neither: at 256 KFs that halves the host analysis.
-    build_sparse_plan((int)a->N, ri, rj, P, 0, 0, dense_tail_min(), false);
-    const bool global_factor = sizeof(double) * ((size_t)(P.S + P.m) * 49 + (size_t)P.m * 7) > kMaxLdsBytes;
-    const bool chip_path = global_factor && cols_path() && P.m <= 512 && (P.nc == 0 || 7 * P.nc + 1 <= 16 * kTailMaxT);
-    if (global_factor && !chip_path)  // split long update lists for the staged global-factor products
-      build_sparse_plan((int)a->N, ri, rj, P, kSplitUpdates, Ly.slot_cap - 1, dense_tail_min(), true);
-    else if (!chip_path)
-      schedule_plan_items(P);
-    PlanImage img;
-    flatten_plan(P, img);
-    // df_factor_kernel's dispatch list: the sparse columns in level order,
-    // DIAG(k) then the OFF tasks of column k, then the dense-tail border tasks
-    meta.off_dfitems = (int)img.data.size();
-    for (int32_t k : P.corder) {
-      img.data.push_back(-1 - k);
-      for (int q = 0; q < P.col_ptr[k + 1] - P.col_ptr[k]; q++) img.data.push_back(P.ctask0[k] + q);
-    }
-    meta.n_dfsparse = (int)img.data.size() - meta.off_dfitems;
-    for (int b = 0; b < P.nc * (P.nc + 1) / 2; b++) img.data.push_back((int32_t)P.task_dst.size() + b);
-    meta.n_dfitems = (int)img.data.size() - meta.off_dfitems;
-    const bool fits = (int64_t)img.data.size() <= Ly.plan_cap && P.S <= Ly.slot_cap;
-    if (fits && !force_dense) {
-      meta.sparse = true;
-      meta.m = P.m;
-      meta.S = P.S;
-      meta.levels = P.levels;
-      meta.plan_len = (int)img.data.size();
-      meta.n_items = (int)P.items.size();
-      meta.n_tasks = (int)P.task_dst.size();
-      meta.n_parts = (int)P.part_q0.size();
-      meta.nc = P.nc;
-      meta.nnz = P.col_ptr.empty() ? 0 : P.col_ptr[P.m];
-      // LDS plan of sparse_llt_kernel<STORE>: flags always, factor + W + y if
-      // they fit, the plan too if it fits as well; else global factor with
-      // per-wave stage areas
-      const size_t flags_bytes =
-          sizeof(int32_t) * (((size_t)(P.S + 2 * P.m + P.part_q0.size()) + 1) & ~size_t(1));
-      const size_t fac_bytes = sizeof(double) * ((size_t)(P.S + P.m) * 49 + (size_t)P.m * 7);
-      const size_t plan_bytes = sizeof(int32_t) * ((img.data.size() + 1) & ~size_t(1));
-      const size_t stage_bytes = sizeof(double) * 16 * (size_t)kStageDoubles;
-      const size_t fin_bytes = sizeof(double) * kFin * (size_t)E;
-      if (fac_bytes + plan_bytes + flags_bytes <= kMaxLdsBytes) {
-        meta.store = 1;
-        meta.lds_bytes = fac_bytes + plan_bytes + flags_bytes;
-      } else if (fac_bytes + flags_bytes <= kMaxLdsBytes) {
-        meta.store = 2;
-        meta.lds_bytes = fac_bytes + flags_bytes;
-      }
-      if (meta.store != 0 && meta.lds_bytes + fin_bytes <= kMaxLdsBytes) {
-        meta.asm_lds = true;
-        meta.lds_bytes += fin_bytes;
-      }
-      if (meta.store == 0) {
-        meta.store = 0;
-        meta.lds_bytes = sizeof(double) * (size_t)P.m * 7 + flags_bytes + stage_bytes;
-        if (meta.lds_bytes > kMaxLdsBytes) meta.sparse = false;  // dense fallback
-      }
-      meta.h_plan = std::move(img.data);
-      img.data.clear();
-      meta.img = img;
-    }
-  }
-  (void)E;
-  return meta;
-}
-
-// The per-call flag state the solve kernels of a plan rely on: the column-
-// task / dataflow / dense-tail epoch flags live only on the global-factor
-// path (the LDS-resident factors keep theirs in LDS), and no tagged granule
-// of an earlier call may match this call's epochs.
-bool reset_plan_flags(const PlanMeta &M, const Layout &Ly, void *ws, hipStream_t st) {
-  bool ok = true;
-  if (!(M.sparse && M.store != 0))
-    ok &= hipMemsetAsync(at<int32_t>(ws, Ly.colsync), 0, Ly.tail - Ly.colsync, st) == hipSuccess;
-  if (M.nc > 0)
-    ok &= hipMemsetAsync(at<double>(ws, Ly.tail) + tail_gran_offset_doubles(), 0,
-                         sizeof(double) * (tail_scratch_doubles() - tail_gran_offset_doubles()), st) == hipSuccess;
-  return ok;
-}
-
-// Upload a plan on the device's side stream and make `st` wait for it: the
-// copy runs while the first linearize kernel does instead of queueing behind
-// it. Callers have waited for every earlier launch on `st` (the prologue's
-// event or a stream sync), so nothing still running there reads `dst`.
-bool upload_plan(Staging *SG, PlanMeta &M, char *dst, hipStream_t st) {
-  if (!(M.sparse && !M.h_plan.empty())) return true;
-  const size_t nb = sizeof(int32_t) * M.h_plan.size();
-  if (SG->plan_pending && hipEventSynchronize(SG->plan_ev) != hipSuccess) return false;
-  SG->plan_pending = false;
-  if (!pinned_reserve(SG->plan_up, SG->plan_cap, nb)) return false;
-  memcpy(SG->plan_up, M.h_plan.data(), nb);
-  bool ok = hipMemcpyAsync(dst, SG->plan_up, nb, hipMemcpyHostToDevice, SG->side) == hipSuccess;
-  ok &= hipEventRecord(SG->plan_ev, SG->side) == hipSuccess;
-  ok &= hipStreamWaitEvent(st, SG->plan_ev, 0) == hipSuccess;
-  SG->plan_pending = ok;
-  return ok;
-}
-
-// Test hook for the bounded waits (tests/test_gpu_backend.py, knob
-// debug_drop_item): drop one item of sparse_llt_kernel's dispatch list, so the
-// items that read its blocks wait on a flag that is never set; the waits time
-// out and the iteration ends as a solve failure (dx = 0) instead of hanging.
-// On the chip-wide path (global factor) the item is dropped from
-// df_factor_kernel's dispatch list instead.
-void apply_drop_item(PlanMeta &M) {
-  const int d = drop_item_knob();
-  if (d < 0 || !M.sparse || M.h_plan.empty()) return;
-  if (M.store == 0 && M.n_dfitems > 0) {
-    int32_t *di = M.h_plan.data() + M.off_dfitems;
-    if (d < M.n_dfitems) {
-      for (int t = d; t + 1 < M.n_dfitems; t++) di[t] = di[t + 1];
-      M.n_dfitems -= 1;
-    }
-    return;
-  }
-  if (M.img.off_wave_ptr >= (int64_t)M.h_plan.size()) return;
-  int32_t *wp = M.h_plan.data() + M.img.off_wave_ptr, *wi = M.h_plan.data() + M.img.off_witems;
-  if (d < wp[1]) {
-    for (int t = d; t + 1 < wp[1]; t++) wi[t] = wi[t + 1];
-    wp[1] -= 1;
-  }
-}
-
-// The host prepare, per solve call (the reference's _unique / searchsorted
-// also synchronise): read ii/jj (+ K) once — the call's only host sync — rank the
-// ids, fetch the plan (or defer it to the first solve) and enqueue ONE
-// upload of everything the launches read (pinned staging, above).
-int gn_prepare_impl(const m3s_gn_args *a, hipStream_t st) {
-  const Layout Ly = gn_layout(a->N, a->HW, a->E);
-  void *ws = a->workspace;
-  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
-  Staging *SG = stage_for_device();
-  if (!SG) return M3S_ELAUNCH;
-  if (SG->pending && hipEventSynchronize(SG->ev) != hipSuccess) return M3S_ELAUNCH;
-  SG->pending = false;
-  const int64_t E = a->E;
-  if (!pinned_reserve(SG->down, SG->down_cap, 64 + 2 * sizeof(int64_t) * (size_t)E)) return M3S_ELAUNCH;
-  float *hK = reinterpret_cast<float *>(SG->down);  // calib intrinsics, read with ii/jj
-  int64_t *hii = reinterpret_cast<int64_t *>(SG->down + 64), *hjj = hii + E;
-  for (int q = 0; q < 9; q++) hK[q] = 0.f;
-  if (a->mode == M3S_MODE_CALIB &&
-      hipMemcpyAsync(hK, a->K, sizeof(float) * 9, hipMemcpyDeviceToHost, st) != hipSuccess)
-    return M3S_ELAUNCH;
-  if (a->N > 1 && a->dx_out && hipMemsetAsync(a->dx_out, 0, sizeof(float) * 7 * (a->N - 1), st) != hipSuccess)
-    return M3S_ELAUNCH;
-  if (E > 0 && hipMemcpyAsync(hii, a->ii, sizeof(int64_t) * E, hipMemcpyDeviceToHost, st) != hipSuccess)
-    return M3S_ELAUNCH;
-  if (E > 0 && hipMemcpyAsync(hjj, a->jj, sizeof(int64_t) * E, hipMemcpyDeviceToHost, st) != hipSuccess)
-    return M3S_ELAUNCH;
-  if (hipStreamSynchronize(st) != hipSuccess) return M3S_ELAUNCH;
-  std::vector<int32_t> ri, rj;
-  const int nu = host_remap(hii, hjj, E, ri, rj);
-  const bool bad = nu > a->N;
-  const bool force_dense = force_dense_knob();
-  PlanMeta meta;
-  bool hit = false;
-  if (!bad && plan_cache_enabled()) {
-    std::lock_guard<std::mutex> g(g_cache_mu);
-    for (size_t q = 0; q < g_cache.size(); q++) {
-      const PlanCacheEntry &C = g_cache[q];
-      if (C.N == a->N && C.HW == a->HW && C.E == E && C.dense == force_dense &&
-          C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
-        meta = C.meta;
-        std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
-        hit = true;
-        break;
-      }
-    }
-  }
-  if (hit && E > 0 && meta.eorder.empty()) build_eorder(meta.rj, 0, E, meta.eorder);  // cached by the prologue path
-  if (!hit) {
-    // ranks and the full-range task table now (the first linearize needs
-    // them); the symbolic plan is built by the first solve of this call,
-    // while the first linearize kernel runs (finish_plan)
-    meta.h_ri = ri;
-    meta.rj = rj;
-    if (E > 0) build_eorder(meta.rj, 0, E, meta.eorder);
-    meta.sparse = !bad && !force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
-    meta.plan_pending = !bad && a->N > 1;
-    meta.force_dense = force_dense;
-  }
-  for (int q = 0; q < 8; q++) meta.h_info[q] = 0;
-  for (int q = 0; q < 64; q++) meta.h_flags[q] = 0;
-  meta.h_info[M3S_INFO_N_UNIQUE] = nu;
-  if (bad) meta.h_info[M3S_INFO_BAD_EDGE] = 1, meta.h_flags[kFlagStop] = 1;
-  if (a->mode == M3S_MODE_CALIB) {  // K row-major: fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]
-    meta.has_K = true;
-    meta.K4[0] = hK[0], meta.K4[1] = hK[4], meta.K4[2] = hK[2], meta.K4[3] = hK[5];
-  }
-  meta.planes_ok = false;
-  meta.range_b = 0, meta.range_e = E, meta.order_ok = E > 0;
-  if (meta.sparse && !meta.plan_pending && meta.lds_bytes > 64 * 1024) set_lds_attributes_once();
-  std::lock_guard<std::mutex> g(g_reg_mu);
-  PlanMeta &M = g_reg[ws];
-  M = std::move(meta);
-  bool ok = true;
-  if (!M.plan_pending) ok &= reset_plan_flags(M, Ly, ws, st);
-  M.epoch = 0;
-  if (!M.plan_pending) apply_drop_item(M);
-  // one upload: flags | rank_i | rank_j | edge counters | edge order [| plan] (the
-  // layout keeps them in this order), then info (the caller's tensor) from
-  // the same buffer
-  const bool with_plan = M.sparse && !M.plan_pending && !M.h_plan.empty();
-  const bool with_tasks = E > 0;
-  size_t n_up = with_plan ? Ly.plan - Ly.flags + sizeof(int32_t) * M.h_plan.size()
-                          : with_tasks ? Ly.eorder - Ly.flags + sizeof(int32_t) * M.eorder.size()
-                                       : Ly.edge_cnt - Ly.flags + edge_cnt_bytes(E);
-  n_up = align_up(n_up, 16);
-  if (!pinned_reserve(SG->up, SG->up_cap, n_up + sizeof M.h_info)) return M3S_ELAUNCH;
-  char *up = SG->up;
-  memcpy(up, M.h_flags, sizeof M.h_flags);
-  memset(up + (Ly.edge_cnt - Ly.flags), 0, edge_cnt_bytes(E));  // the fused finalize's counters
-  if (E > 0) {
-    memcpy(up + (Ly.rank_i - Ly.flags), M.h_ri.data(), sizeof(int32_t) * E);
-    memcpy(up + (Ly.rank_j - Ly.flags), M.rj.data(), sizeof(int32_t) * E);
-  }
-  if (with_tasks) memcpy(up + (Ly.eorder - Ly.flags), M.eorder.data(), sizeof(int32_t) * M.eorder.size());
-  if (with_plan) memcpy(up + (Ly.plan - Ly.flags), M.h_plan.data(), sizeof(int32_t) * M.h_plan.size());
-  memcpy(up + n_up, M.h_info, sizeof M.h_info);
-  ok &= hipMemcpyAsync(at<char>(ws, Ly.flags), up, n_up, hipMemcpyHostToDevice, st) == hipSuccess;
-  ok &= hipMemcpyAsync(a->info, up + n_up, sizeof M.h_info, hipMemcpyHostToDevice, st) == hipSuccess;
-  ok &= hipEventRecord(SG->ev, st) == hipSuccess;
-  SG->pending = ok;
-  return ok ? M3S_OK : M3S_ELAUNCH;
-}
-
-// The deferred half of a cold prepare: the symbolic plan (ordering, fill,
-// update lists; build_plan_meta) on the host, its upload, and the per-plan
-// flag resets. Called by a call's first solve, i.e. after its first
-// linearize is on the stream: the analysis runs while that kernel does.
-int finish_plan(const m3s_gn_args *a, const Layout &Ly, hipStream_t st) {
-  void *ws = a->workspace;
-  std::vector<int32_t> ri, rj;
-  bool force_dense;
-  {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    auto it = g_reg.find(ws);
-    if (it == g_reg.end()) return M3S_EINVAL;
-    if (!it->second.plan_pending) return M3S_OK;
-    ri = it->second.h_ri;
-    rj = it->second.rj;
-    force_dense = it->second.force_dense;
-  }
-  PlanMeta built = build_plan_meta(a, Ly, ri, rj, force_dense);
-  if (built.sparse && built.lds_bytes > 64 * 1024) set_lds_attributes_once();
-  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
-  Staging *SG = stage_for_device();
-  if (!SG) return M3S_ELAUNCH;
-  if (SG->plan_pending && hipEventSynchronize(SG->plan_ev) != hipSuccess) return M3S_ELAUNCH;
-  SG->plan_pending = false;
-  std::lock_guard<std::mutex> g(g_reg_mu);
-  PlanMeta &M = g_reg[ws];
-  M.sparse = built.sparse, M.store = built.store, M.asm_lds = built.asm_lds, M.lds_bytes = built.lds_bytes;
-  M.m = built.m, M.S = built.S, M.levels = built.levels, M.plan_len = built.plan_len;
-  M.n_items = built.n_items, M.n_tasks = built.n_tasks, M.n_parts = built.n_parts, M.nc = built.nc;
-  M.off_dfitems = built.off_dfitems, M.n_dfitems = built.n_dfitems, M.nnz = built.nnz;
-  M.n_dfsparse = built.n_dfsparse;
-  M.img = built.img;
-  M.h_plan = std::move(built.h_plan);
-  M.plan_pending = false;
-  if (plan_cache_enabled()) {
-    PlanCacheEntry C;
-    C.N = a->N, C.HW = a->HW, C.E = a->E, C.dense = force_dense, C.ri = ri, C.rj = rj;
-    C.tail_min = dense_tail_min();
-    C.meta = M;
-    std::lock_guard<std::mutex> gc(g_cache_mu);
-    g_cache.insert(g_cache.begin(), std::move(C));
-    if (g_cache.size() > kPlanCacheSize) g_cache.pop_back();
-  }
-  bool ok = reset_plan_flags(M, Ly, ws, st);
-  apply_drop_item(M);
-  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
-  return ok ? M3S_OK : M3S_ELAUNCH;
-}
-
-// The host half of an async prepare (gn_prepare_async), at the first point a
-// call needs its ids on the host (its first solve, or a sharded rank's edge
-// range): wait for the prologue (normally long done: the first linearize is
-// queued behind it), read ii / jj / K from the pinned slot, rank the ids on
-// the host (the plan and its cache key need them), and fetch the cached plan;
-// a miss leaves the plan to finish_plan. The linearize state of the entry
-// (range, task table, planes) is the prologue's and stays.
-int host_finish(const m3s_gn_args *a, hipStream_t st) {
-  void *ws = a->workspace;
-  int slot = -1;
-  {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    auto it = g_reg.find(ws);
-    if (it == g_reg.end()) return M3S_EINVAL;
-    if (!it->second.host_pending) return M3S_OK;
-    slot = it->second.slot;
-  }
-  const int64_t E = a->E;
-  std::vector<int64_t> hii((size_t)E), hjj((size_t)E);
-  float hK[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  {
-    std::lock_guard<std::mutex> stage_lock(g_stage_mu);
-    Staging *SG = stage_for_device();
-    if (!SG || slot < 0 || slot >= (int)SG->slots.size()) return M3S_ELAUNCH;
-    DownSlot &D = SG->slots[slot];
-    if (hipEventSynchronize(D.ev) != hipSuccess) return M3S_ELAUNCH;
-    if (a->mode == M3S_MODE_CALIB) memcpy(hK, D.p, sizeof hK);
-    if (E > 0) {
-      memcpy(hii.data(), D.p + 64, sizeof(int64_t) * (size_t)E);
-      memcpy(hjj.data(), D.p + 64 + sizeof(int64_t) * (size_t)E, sizeof(int64_t) * (size_t)E);
-    }
-    D.busy = false;
-  }
-  std::vector<int32_t> ri, rj;
-  const int nu = host_remap(hii.data(), hjj.data(), E, ri, rj);
-  const bool bad = nu > a->N;  // the prologue has stopped the call (flags, info)
-  const Layout Ly = gn_layout(a->N, a->HW, a->E);
-  bool force_dense;
-  {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    force_dense = g_reg.at(ws).force_dense;
-  }
-  PlanMeta hitm;
-  bool hit = false;
-  if (!bad && plan_cache_enabled()) {
-    std::lock_guard<std::mutex> g(g_cache_mu);
-    for (size_t q = 0; q < g_cache.size(); q++) {
-      const PlanCacheEntry &C = g_cache[q];
-      if (C.N == a->N && C.HW == a->HW && C.E == E && C.dense == force_dense &&
-          C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
-        hitm = C.meta;
-        std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
-        hit = true;
-        break;
-      }
-    }
-  }
-  if (hit && hitm.sparse && hitm.lds_bytes > 64 * 1024) set_lds_attributes_once();
-  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
-  Staging *SG = stage_for_device();
-  if (!SG) return M3S_ELAUNCH;
-  std::lock_guard<std::mutex> g(g_reg_mu);
-  PlanMeta &M = g_reg[ws];
-  M.host_pending = false, M.slot = -1;
-  M.h_ri = std::move(ri), M.rj = std::move(rj);
-  M.K4[0] = hK[0], M.K4[1] = hK[4], M.K4[2] = hK[2], M.K4[3] = hK[5];
-  if (bad) {
-    M.sparse = false, M.plan_pending = false;
-    return M3S_OK;
-  }
-  if (!hit) return M3S_OK;  // plan_pending: finish_plan builds it
-  M.sparse = hitm.sparse, M.store = hitm.store, M.asm_lds = hitm.asm_lds, M.lds_bytes = hitm.lds_bytes;
-  M.m = hitm.m, M.S = hitm.S, M.levels = hitm.levels, M.plan_len = hitm.plan_len;
-  M.n_items = hitm.n_items, M.n_tasks = hitm.n_tasks, M.n_parts = hitm.n_parts, M.nc = hitm.nc;
-  M.off_dfitems = hitm.off_dfitems, M.n_dfitems = hitm.n_dfitems, M.nnz = hitm.nnz;
-  M.n_dfsparse = hitm.n_dfsparse;
-  M.img = hitm.img;
-  M.h_plan = std::move(hitm.h_plan);
-  M.plan_pending = false;
-  bool ok = reset_plan_flags(M, Ly, ws, st);
-  apply_drop_item(M);
-  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
-  return ok ? M3S_OK : M3S_ELAUNCH;
-}
-
-// Prepare a call without a host round trip: one prologue kernel on the stream
-// (ranks, task table, flags, info, dx_out; the ids to pinned memory) and the
-// registry entry; the host reads the ids later (host_finish), while the first
-// linearize runs. Large edge sets (> kProMaxE) take the synchronous prepare.
-int gn_prepare_async(const m3s_gn_args *a, hipStream_t st) {
-  const int64_t E = a->E;
-  if (E > kProMaxE || a->N > (int64_t)1 << 30 || knob<K_prologue>() == 0) return gn_prepare_impl(a, st);
-  const Layout Ly = gn_layout(a->N, a->HW, E);
-  void *ws = a->workspace;
-  std::lock_guard<std::mutex> stage_lock(g_stage_mu);
-  Staging *SG = stage_for_device();
-  if (!SG) return M3S_ELAUNCH;
-  const int slot = acquire_slot(*SG, 64 + 2 * sizeof(int64_t) * (size_t)E);
-  if (slot < 0) return M3S_ELAUNCH;
-  DownSlot &D = SG->slots[slot];
-  ProArgs P;
-  P.ii = a->ii, P.jj = a->jj;
-  P.K = a->mode == M3S_MODE_CALIB ? a->K : nullptr;
-  P.down_K = reinterpret_cast<float *>(D.dp);
-  P.down_ii = reinterpret_cast<int64_t *>(D.dp + 64);
-  P.down_jj = P.down_ii + E;
-  P.E = (int)E, P.N = (int)a->N, P.P2 = prologue_p2(E);
-  P.flags = at<int32_t>(ws, Ly.flags), P.rank_i = at<int32_t>(ws, Ly.rank_i), P.rank_j = at<int32_t>(ws, Ly.rank_j);
-  P.eorder = at<int32_t>(ws, Ly.eorder), P.info = a->info, P.edge_cnt = at<uint32_t>(ws, Ly.edge_cnt);
-  P.dx_out = a->dx_out;
-  P.n_dx = (a->N > 1 && a->dx_out) ? (int)(7 * (a->N - 1)) : 0;
-  const size_t lds = prologue_lds(P.E, P.P2);
-  if (lds > 64 * 1024) set_lds_attributes_once();
-  gn_prologue_kernel<<<1, kProThreads, lds, st>>>(P);
-  if (launch_ok() != M3S_OK || hipEventRecord(D.ev, st) != hipSuccess) {
-    D.busy = false;
-    return M3S_ELAUNCH;
-  }
-  PlanMeta meta;
-  meta.host_pending = true, meta.slot = slot;
-  meta.has_K = a->mode == M3S_MODE_CALIB;
-  meta.force_dense = force_dense_knob();
-  meta.sparse = !meta.force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
-  meta.plan_pending = a->N > 1;
-  meta.range_b = 0, meta.range_e = E, meta.order_ok = E > 0;
-  std::lock_guard<std::mutex> g(g_reg_mu);
-  PlanMeta &M = g_reg[ws];
-  if (M.host_pending && M.slot >= 0 && M.slot < (int)SG->slots.size() && M.slot != slot)
-    SG->slots[M.slot].busy = false;  // a re-prepare of a workspace whose ids were never read
-  M = std::move(meta);
-  M.epoch = 0;
-  return M3S_OK;
-}
-
-int gn_linearize_impl(const m3s_gn_args *a, const ResidualParams &P, int64_t eb, int64_t ee,
-                      double *edge_sums, hipStream_t st, bool fuse_fin = false, int64_t *chunks_used = nullptr) {
-  const Layout Ly = gn_layout(a->N, a->HW, a->E);
-  void *ws = a->workspace;
-  const int64_t E_loc = ee - eb;
-  if (E_loc <= 0) return M3S_OK;
-  LinArgs L{};
-  L.Twc = a->Twc;
-  L.T_rel = nullptr;
-  L.Xs = a->Xs;
-  L.Cs = a->Cs;
-  L.Xsrc = nullptr;
-  L.idx = a->idx_ii2jj;
-  L.idx32 = a->idx_i32 ? 1 : 0;
-  L.valid = a->valid_match;
-  L.Q = a->Q;
-  L.rank_i = at<int32_t>(ws, Ly.rank_i);
-  L.rank_j = at<int32_t>(ws, Ly.rank_j);
-  L.stop = at<int32_t>(ws, Ly.flags) + kFlagStop;
-  L.partials = at<float>(ws, Ly.partials);
-  L.planes = at<float>(ws, Ly.planes);
-  L.eorder = nullptr;
-  L.cnt_base = 0;
-  // fused finalize only over the whole edge set (single-GPU solve); fused
-  // edge sums for the stepwise API (any range)
-  const bool fin_tail = fuse_fin && eb == 0 && ee == a->E;
-  L.edge_cnt = (fin_tail || edge_sums) ? at<uint32_t>(ws, Ly.edge_cnt) : nullptr;
-  L.esum = fin_tail ? nullptr : edge_sums;
-  L.fin = at<double>(ws, Ly.fin);
-  L.HW = a->HW;
-  L.edge_begin = eb;
-  L.E_loc = E_loc;
-  L.P = P;
-  L.Kd = a->mode == M3S_MODE_CALIB ? a->K : nullptr;
-  const bool vec = (a->HW % 4 == 0) && vec_ok(a->Xs, 16) && vec_ok(a->Cs, 16) && vec_ok(a->Q, 16) &&
-                   vec_ok(a->idx_ii2jj, 16) && vec_ok(a->valid_match, 4);
-  // (the packed and pipelined gathering kernels address a pointmap through
-  // 32-bit buffer offsets: 12 HW bytes must fit a signed int)
-  const bool can_pack = vec && a->HW * 12 < ((int64_t)1 << 31) &&
-                        (a->mode != M3S_MODE_CALIB || (a->width < 65536 && a->height < 32768));
-  int pack = 0;
-  bool ordered = false;
-  if (eb != 0 || ee != a->E) {  // a sharded rank's range: its edge order is built from the host ranks
-    const int rc = host_finish(a, st);
-    if (rc) return rc;
-  }
-  {
-    std::lock_guard<std::mutex> stage_lock(g_stage_mu);  // (lock order: staging, then registry)
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    auto it = g_reg.find(ws);
-    if (it == g_reg.end()) return M3S_EINVAL;  // m3s_gn_prepare not called on this workspace
-    PlanMeta &M = it->second;
-    if (M.range_b != eb || M.range_e != ee) {  // a sharded rank's own edge range
-      M.range_b = eb, M.range_e = ee, M.planes_ok = false, M.order_ok = false;
-      if (M.cnt_arr) M.cnt_ok = false;
-      if ((int64_t)M.rj.size() >= ee) {
-        std::vector<int32_t> order;
-        build_eorder(M.rj, eb, E_loc, order);
-        // uploaded from pinned staging guarded by an event, so the registry
-        // entry owns no host memory a queued copy still reads (m3s_gn_release
-        // need not synchronise)
-        Staging *SG = stage_for_device();
-        const size_t nb = sizeof(int32_t) * order.size();
-        if (!SG) return M3S_ELAUNCH;
-        if (SG->tasks_pending && hipEventSynchronize(SG->tasks_ev) != hipSuccess) return M3S_ELAUNCH;
-        SG->tasks_pending = false;
-        if (!pinned_reserve(SG->tasks_up, SG->tasks_cap, nb)) return M3S_ELAUNCH;
-        memcpy(SG->tasks_up, order.data(), nb);
-        if (hipMemcpyAsync(at<int32_t>(ws, Ly.eorder), SG->tasks_up, nb, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipEventRecord(SG->tasks_ev, st) != hipSuccess)
-          return M3S_ELAUNCH;
-        SG->tasks_pending = true;
-        M.order_ok = true;
-      }
-    }
-    ordered = M.order_ok;
-    if (can_pack) {
-      pack = M.planes_ok ? 2 : 1;
-      M.planes_ok = true;
-    }
-    // chunking: the gathering kernel's own (smaller chunks); the packed kernel
-    // counts its arrivals after the first iteration's (edge_tail)
-    const int64_t c_gather = chunks_for(a->HW, E_loc, kGatherBlocks);
-    L.chunks = pack == 2 ? chunks_for(a->HW, E_loc) : c_gather;
-    L.cnt_base = pack == 2 ? (uint32_t)c_gather : 0u;
-    if (fin_tail) {
-      M.cnt_ok = false;  // the drop-in call counts from its own prepare
-    } else if (L.esum) {
-      if (!M.cnt_ok) {  // stale arrivals: zero every counter (a few KB)
-        if (hipMemsetAsync(L.edge_cnt, 0, edge_cnt_bytes(a->E), st) != hipSuccess) return M3S_ELAUNCH;
-        M.cnt_arr = 0, M.cnt_ok = true;
-      }
-      L.cnt_base = M.cnt_arr;
-      M.cnt_arr += (uint32_t)L.chunks;
-    }
-  }
-  L.chunk_pix = chunk_pixels(a->HW, L.chunks);
-  const int64_t T = E_loc * L.chunks;
-  L.per = (T + 7) / 8;
-  int64_t blocks = T;
-  if (ordered) {
-    L.eorder = at<int32_t>(ws, Ly.eorder);
-    blocks = 8 * L.per;
-  }
-  if (chunks_used) *chunks_used = L.chunks;
-  int rc = dispatch_linearize<false>(a->mode, L, blocks, vec, pack, st);
-  if (rc && L.esum) {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    auto it = g_reg.find(ws);
-    if (it != g_reg.end()) it->second.cnt_ok = false;  // arrivals unknown
-  }
-  return rc;  // NULL edge_sums: partials only (kernel timing)
-}
-
-// edge_sums: per-edge local sums (stepwise API), or NULL with `partials` of
-// `chunks` chunks per edge (single-GPU call: no separate reduce launch).
-int gn_solve_impl(const m3s_gn_args *a, const double *edge_sums, const float *partials, int64_t chunks,
-                  hipStream_t st, bool fin_ready = false) {
-  const Layout Ly = gn_layout(a->N, a->HW, a->E);
-  void *ws = a->workspace;
-  int32_t *flags = at<int32_t>(ws, Ly.flags);
-  int32_t *stop = flags + kFlagStop;
-  const int64_t n = Ly.n, ld = Ly.ld;
-  if (a->N <= 1) return M3S_OK;
-  int rc0 = host_finish(a, st);
-  if (rc0) return rc0;
-  rc0 = finish_plan(a, Ly, st);
-  if (rc0) return rc0;
-  PlanMeta meta;
-  {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    auto it = g_reg.find(ws);
-    if (it == g_reg.end()) return M3S_EINVAL;  // m3s_gn_prepare not called on this workspace
-    meta = solve_view(it->second);
-    it->second.epoch++;
-  }
-  int rc;
-  float *dx = a->dx_out;
-  if (meta.sparse) {
-    double *fin = at<double>(ws, Ly.fin);
-    if (a->E > 0 && !fin_ready) {
-      finalize_edges_kernel<<<dim3((unsigned)a->E), dim3(64), 0, st>>>(
-          edge_sums, edge_sums ? nullptr : partials, chunks, at<int32_t>(ws, Ly.rank_i), a->Twc, fin, stop);
-      if ((rc = launch_ok())) return rc;
-    }
-    const PlanImage &I = meta.img;
-    SparseDev D;
-    D.phase = 0;
-    D.tail_done = 0;
-    D.tail_A = nullptr;
-    D.tail_ld = 0;
-    D.plan = at<int32_t>(ws, Ly.plan);
-    D.plan_len = meta.plan_len;
-    const int64_t offs[kPlanSections] = {
-        I.off_perm,     I.off_col_ptr,      I.off_col_row,  I.off_col_slot, I.off_lev_ptr,
-        I.off_lev_col,  I.off_dtr_ptr,      I.off_dtr_slot, I.off_dtr_p,    I.off_task_lev_ptr,
-        I.off_task_dst, I.off_task_col,     I.off_task_tr_ptr, I.off_tr_a,  I.off_tr_b,
-        I.off_asm_ptr,  I.off_asm_edge,     I.off_g_ptr,    I.off_g_edge,   I.off_ctask_ptr,
-        I.off_items,    I.off_wave_ptr,     I.off_witems,
-        I.off_part_q0,  I.off_part_q1,      I.off_part_tgt, I.off_dpart_ptr, I.off_opart_ptr, I.off_clq,
-        I.off_corder,   I.off_ctask0};
-    for (int q = 0; q < kPlanSections; q++) D.off[q] = (int)offs[q];
-    D.n_items = meta.n_items;
-    D.n_tasks = meta.n_tasks;
-    D.n_parts = meta.n_parts;
-    D.nc = meta.nc;
-    D.E = (int)a->E;
-    D.asm_lds = meta.asm_lds ? 1 : 0;
-    D.parts = at<double>(ws, Ly.parts);
-    D.dbg = at<int64_t>(ws, Ly.A);
-    D.m = meta.m;
-    D.S = meta.S;
-    D.levels = meta.levels;
-    D.L = at<double>(ws, Ly.Lblk);
-    D.rhs = at<double>(ws, Ly.rhs);
-    if (!meta.asm_lds) {  // multi-workgroup assembly into the global factor array
-      assemble_slots_kernel<<<dim3((unsigned)(meta.S + meta.m)), dim3(64), 0, st>>>(
-          fin, D.plan, (int)I.off_asm_ptr, (int)I.off_asm_edge, (int)I.off_g_ptr, (int)I.off_g_edge, meta.m,
-          meta.S, D.L, at<double>(ws, Ly.rhs), stop);
-      if ((rc = launch_ok())) return rc;
-    }
-    D.Dinv = at<double>(ws, Ly.Dinv);
-    D.fin = fin;
-    D.Twc = a->Twc;
-    D.N = a->N;
-    D.dx_out = dx;
-    D.info = a->info;
-    D.flags = flags;
-    D.delta_thresh = a->delta_thresh;
-    if (meta.store == 0 && cols_path() && meta.m <= 512 && (meta.nc == 0 || 7 * meta.nc + 1 <= 16 * kTailMaxT)) {
-      // column tasks over the chip -> tail border -> dense tail on the MFMA
-      // -> column back-substitution + step
-      ColArgs C;
-      C.plan = D.plan;
-      for (int q = 0; q < kPlanSections; q++) C.off[q] = D.off[q];
-      C.m = meta.m;
-      C.c0 = meta.m - meta.nc;
-      C.ncols = C.c0;
-      C.epoch = meta.epoch;
-      C.L = D.L;
-      C.Dinv = D.Dinv;
-      C.y = const_cast<double *>(D.rhs);
-      int32_t *cs = at<int32_t>(ws, Ly.colsync);
-      C.done = cs;
-      C.done2 = cs + (meta.m + 1);
-      C.ctr = cs + 2 * (meta.m + 1);
-      C.flags = flags;
-      C.info = a->info;
-      C.Twc = a->Twc;
-      C.dx_out = dx;
-      C.N = a->N;
-      C.delta_thresh = a->delta_thresh;
-      double *tail = at<double>(ws, Ly.tail);
-      const int tld = 16 * kTailMaxT;
-      bool gcomb_used = false;  // the tail launch also ran the sparse back-substitution
-      // the factor launch (df_factor_kernel)
-      if (df_path()) {
-        // every block of the sparse columns and the tail border: one wave-level dataflow
-        DfArgs F;
-        F.plan = D.plan;
-        for (int q = 0; q < kPlanSections; q++) F.off[q] = D.off[q];
-        F.items = D.plan + meta.off_dfitems;
-        F.n_items = meta.n_dfitems;
-        F.n_tasks = meta.n_tasks;
-        F.m = meta.m;
-        F.c0 = C.c0;
-        F.nc = meta.nc;
-        F.epoch = meta.epoch;
-        F.L = D.L;
-        F.Dinv = D.Dinv;
-        F.y = C.y;
-        F.sdone = cs + 2 * (meta.m + 1) + 16;
-        F.ctr = C.ctr + 3;
-        F.flags = flags;
-        F.tail_A = tail;
-        F.tail_ld = tld;
-        F.Wgr = at<double>(ws, Ly.wgran);
-        const int nw = std::max(1, std::min(F.n_items, 1024));
-        if (F.n_items > 0) df_factor_kernel<<<(nw + kDfWaves - 1) / kDfWaves, 64 * kDfWaves, 0, st>>>(F);
-      } else {
-#ifdef M3S_TEST_PATHS
-        const int g1 = std::max(1, std::min(C.ncols, 256));
-        col_factor_kernel<<<g1, 256, 0, st>>>(C);
-#endif
-      }
-      // the dense tail's launch
-      if (meta.nc > 0) {
-        D.tail_A = tail;
-        D.tail_ld = tld;
-        const int nt0 = meta.nc * (meta.nc + 1) / 2;
-        if (!df_path())
-          border_kernel<<<(nt0 + kBorderWaves - 1) / kBorderWaves, 64 * kBorderWaves,
-                          kBorderWaves * kStageDoubles * sizeof(double), st>>>(D);
-        TailArgs T;
-        T.Ad = tail;
-        T.ld = tld;
-        T.rhs = C.y;
-        T.Lg = tail + (size_t)tld * tld;
-        T.Wg = T.Lg + (size_t)kTailMaxT * (kTailMaxT + 1) / 2 * 256;
-        T.flags = flags;
-        T.nc = meta.nc;
-        T.c0 = C.c0;
-        if (tail_cyc()) {
-          TailSync Y;
-          Y.tflag = cs + 2 * (meta.m + 1) + 16 + Ly.slot_cap;
-          Y.epoch = meta.epoch;
-          Y.ypg = T.Wg + (size_t)kTailMaxT * 256;
-          Y.LgT = Y.ypg + 16 * kTailMaxT;
-          Y.LgG = tail + tail_gran_offset_doubles();
-          Y.warm = tail_warm_knob() ? 1 : 0;
-          const int TC = (7 * meta.nc + 15) / 16;
-          // the sparse back-substitution on extra workgroups of the tail's
-          // launch (gcol_worker) when there are sparse columns
-          GArgs G;
-          G.X = nullptr;
-          G.n_pairs = (TC + 1) / 2;
-          G.nx = ((1 + 7 * meta.nc) + 7) / 8 * 8;
-          G.task = C.ctr + 8, G.comb = C.ctr + 9, G.fin = C.ctr + 10, G.xt_ready = C.ctr + 11;
-          G.cnt = Y.tflag + 2 * kTailMaxT;
-          int nG = 0;
-          if (gcomb_knob() && meta.nc >= gcomb_min_nc_knob() && tail_pair_path() && C.ncols > 0) {
-            G.X = at<double>(ws, Ly.gx);
-            nG = std::max(1, std::min(C.ncols, std::min(gcomb_wg_knob(), 240 - G.n_pairs)));
-            gcomb_used = true;
-          }
-          const unsigned gt = (unsigned)(G.n_pairs + nG);
-          if (tail_pair_path())
-            if (((7 * meta.nc + 16) / 16 + 2) / 3 <= 7)  // tile rows TR: rows per wave of waves 1..3
-              tail_pair_kernel<7><<<gt, 64 * kTailNW, 0, st>>>(T, Y, C, G);
-            else
-              tail_pair_kernel<(kTailMaxT + 2) / 3><<<gt, 64 * kTailNW, 0, st>>>(T, Y, C, G);
-          else
-            tail_cyc_kernel<<<TC, 64 * kTailNW, 0, st>>>(T, Y);
-        } else {
-          tail_llt_kernel<<<1, 64 * kTailNW, 0, st>>>(T);
-        }
-      }
-      if (!gcomb_used) {
-        const int g4 = std::max(1, std::min(C.ncols, 256));
-        col_backsub_kernel<<<g4, 64, 0, st>>>(C);
-      }
-    } else if (meta.store == 1)
-      if (g_slv_ext_ev) {
-        hipExtLaunchKernelGGL(sparse_llt_kernel<1>, dim3(1), dim3(1024), meta.lds_bytes, st, g_slv_ext_ev[0],
-                              g_slv_ext_ev[1], 0, D);
-        g_slv_ext_ev = nullptr;
-      } else {
-        sparse_llt_kernel<1><<<1, 1024, meta.lds_bytes, st>>>(D);
-      }
-    else if (meta.store == 2)
-      sparse_llt_kernel<2><<<1, 1024, meta.lds_bytes, st>>>(D);
-    else if (meta.nc > 0 && border_split()) {
-      // the dense tail on the f64 MFMA when it fits (tail_llt_kernel), else
-      // in phase 2 of the one-workgroup kernel
-      const bool mfma_tail = 7 * meta.nc + 1 <= 16 * kTailMaxT && tail_mfma();
-      double *tail = at<double>(ws, Ly.tail);
-      const int tld = 16 * kTailMaxT;
-      D.tail_A = mfma_tail ? tail : nullptr;
-      D.tail_ld = tld;
-      D.phase = 1;
-      sparse_llt_kernel<0><<<1, 1024, meta.lds_bytes, st>>>(D);
-      const int nt0 = meta.nc * (meta.nc + 1) / 2;
-      border_kernel<<<(nt0 + kBorderWaves - 1) / kBorderWaves, 64 * kBorderWaves,
-                      kBorderWaves * kStageDoubles * sizeof(double), st>>>(D);
-      if (mfma_tail) {
-        TailArgs T;
-        T.Ad = tail;
-        T.ld = tld;
-        T.rhs = const_cast<double *>(D.rhs);
-        T.Lg = tail + (size_t)tld * tld;
-        T.Wg = T.Lg + (size_t)kTailMaxT * (kTailMaxT + 1) / 2 * 256;
-        T.flags = flags;
-        T.nc = meta.nc;
-        T.c0 = meta.m - meta.nc;
-        tail_llt_kernel<<<1, 64 * kTailNW, 0, st>>>(T);
-        D.tail_done = 1;
-      }
-      D.phase = 2;
-      sparse_llt_kernel<0, true><<<1, 1024, meta.lds_bytes, st>>>(D);
-    } else
-      sparse_llt_kernel<0><<<1, 1024, meta.lds_bytes, st>>>(D);
-    return launch_ok();
-  }
-  // dense fallback: RHS-augmented system, register or tiled LLT
-  if (!edge_sums && a->E > 0) {
-    double *es = at<double>(ws, Ly.edge_sums);
-    edge_reduce_kernel<<<dim3((unsigned)a->E), dim3(64), 0, st>>>(partials, chunks, es, stop);
-    if ((rc = launch_ok())) return rc;
-    edge_sums = es;
-  }
-  double *A = at<double>(ws, Ly.A);
-  assemble_kernel<<<dim3((unsigned)a->N), dim3(256), 0, st>>>(
-      edge_sums, at<int32_t>(ws, Ly.rank_i), at<int32_t>(ws, Ly.rank_j), a->E, a->Twc, n, ld, A, stop);
-  if ((rc = launch_ok())) return rc;
-  const int np = (int)n + 1;
-#ifdef M3S_TEST_PATHS
-  if (np <= kMaxSmallNp) {
-    const int nbc = (np + 31) / 32;
-#define M3S_CHOL(NB)                                                                                   \
-  case NB:                                                                                             \
-    chol_small_kernel<NB><<<dim3(1), dim3(kCholThreads), 0, st>>>(A, ld, (int)n, a->Twc, a->N, dx, \
-                                                                 a->info, stop, a->delta_thresh);  \
-    break;
-    switch (nbc) {
-      M3S_CHOL(1)
-      M3S_CHOL(2)
-      M3S_CHOL(3)
-      M3S_CHOL(4)
-      M3S_CHOL(5)
-      M3S_CHOL(6)
-      M3S_CHOL(7)
-      default:
-        return M3S_ETOOLARGE;
-    }
-#undef M3S_CHOL
-    return launch_ok();
-  }
-#endif
-  (void)np;
-  const int nt = (int)(ld / kTile);
-  for (int kb = 0; kb < nt; kb++) {
-    if ((int64_t)kb * kTile >= n) break;
-    potrf_tile_kernel<<<1, 256, 0, st>>>(A, ld, n, kb, flags);
-    const int mt = nt - kb - 1;
-    if (mt > 0) {
-      trsm_tile_kernel<<<mt, 256, 0, st>>>(A, ld, n, kb, flags);
-      update_tiles_kernel<<<mt * (mt + 1) / 2, 256, 0, st>>>(A, ld, kb, flags);
-    }
-    if ((rc = launch_ok())) return rc;
-  }
-  const size_t smem = sizeof(double) * (size_t)(ld + kTile * (kTile + 1)) + sizeof(float) * (size_t)ld;
-  backsolve_kernel<<<1, 1024, smem, st>>>(A, ld, (int)n, a->Twc, a->N, dx, a->info, flags, a->delta_thresh);
-  return launch_ok();
-}
-
-void set_lds_attributes_once() {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sparse_llt_kernel<0>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sparse_llt_kernel<0, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sparse_llt_kernel<1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sparse_llt_kernel<2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gn_prologue_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes);
-  });
-}
-
-// In-call launch timing (bench.py's roofline leg, m3s_debug_call_timing):
-// when on, a drop-in call records a timing event on its stream before each
-// linearize launch, after it and after the solve launches of that iteration,
-// so the packed kernel is timed in the call's own launch pattern (behind the
-// previous iteration's solve), not back to back. Kinds: 0 first-iteration
-// (gathering) linearize, 1 packed linearize, 2 solve (every launch of it).
-struct CallTiming {
-  std::mutex mu;
-  bool on = false;
-  std::vector<hipEvent_t> ev;  // pool, reused
-  std::vector<int> kind;       // kind of the span from event q to q + 1 (-1: none)
-  size_t used = 0;
-  std::vector<hipEvent_t> kev;  // pool: {start, stop} of each timed linearize dispatch
-  std::vector<char> kev_ok;     // per pair: the dispatch took it (else the span uses ev[q], ev[q + 1])
-  size_t kused = 0;
-};
-CallTiming &call_timing() {
-  static CallTiming t;
-  return t;
-}
-bool call_mark(hipStream_t st, int kind_next) {  // caller holds the lock
-  CallTiming &T = call_timing();
-  if (T.used == T.ev.size()) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return false;
-    T.ev.push_back(e);
-    T.kind.push_back(-1);
-  }
-  T.kind[T.used] = kind_next;
-  return hipEventRecord(T.ev[T.used++], st) == hipSuccess;
-}
-
-int gn_full(const m3s_gn_args *a, int mode, void *stream) {
-  int rc = check_args(a);
-  if (rc) return rc;
-  if (a->mode != mode) return M3S_EINVAL;
-  if (gn_layout(a->N, a->HW, a->E).ld > kMaxLd) return M3S_ETOOLARGE;
-  hipStream_t st = S(stream);
-  const ResidualParams P = make_params(a);  // calib intrinsics: read by the kernels (LinArgs::Kd)
-  if ((rc = gn_prepare_async(a, st))) return rc;
-  const Layout Ly = gn_layout(a->N, a->HW, a->E);
-  const float *partials = at<float>(a->workspace, Ly.partials);
-  bool sparse;
-  {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    sparse = g_reg.at(a->workspace).sparse;
-  }
-  CallTiming &CT = call_timing();
-  std::unique_lock<std::mutex> tl(CT.mu, std::defer_lock);
-  bool timing = false;
-  {
-    std::lock_guard<std::mutex> g(CT.mu);
-    timing = CT.on;
-  }
-  if (timing) tl.lock();
-  // sparse solve: the linearize kernels finalize each edge themselves
-  for (int it = 0; it < a->max_iter; it++) {
-    int64_t chunks = 0;  // of this iteration's linearize launch (the dense path reduces its partials)
-    if (timing && !call_mark(st, it == 0 ? 0 : 1)) return M3S_ELAUNCH;
-    if (timing) {  // the linearize dispatch's own begin / end (launch_lin)
-      while (CT.kev.size() < CT.kused + 2) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return M3S_ELAUNCH;
-        CT.kev.push_back(e);
-      }
-      if (CT.kev_ok.size() < CT.kev.size() / 2) CT.kev_ok.resize(CT.kev.size() / 2);
-      g_lin_ext_ev = &CT.kev[CT.kused];
-    }
-    rc = gn_linearize_impl(a, P, 0, a->E, nullptr, st, sparse, &chunks);
-    if (timing) {
-      CT.kev_ok[CT.kused / 2] = g_lin_ext_ev == nullptr;  // launch_lin took the pair
-      CT.kused += 2;
-    }
-    g_lin_ext_ev = nullptr;
-    if (rc) return rc;
-    if (timing && !call_mark(st, 2)) return M3S_ELAUNCH;
-    if (timing) {  // the solve dispatch's own begin / end when it is one launch (sparse_llt_kernel<1>)
-      while (CT.kev.size() < CT.kused + 2) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return M3S_ELAUNCH;
-        CT.kev.push_back(e);
-      }
-      if (CT.kev_ok.size() < CT.kev.size() / 2) CT.kev_ok.resize(CT.kev.size() / 2);
-      g_slv_ext_ev = &CT.kev[CT.kused];
-    }
-    rc = gn_solve_impl(a, nullptr, partials, chunks, st, sparse);
-    if (timing) {
-      CT.kev_ok[CT.kused / 2] = g_slv_ext_ev == nullptr;
-      CT.kused += 2;
-    }
-    g_slv_ext_ev = nullptr;
-    if (rc) return rc;
-    if (timing && !call_mark(st, -1)) return M3S_ELAUNCH;
-  }
-  return M3S_OK;
-}
-
-}  // namespace
-
+#include "gn/knobs.h"
+#include "gn/launch.h"
+#include "gn/plan.h"
+#include "gn/iterate.h"
 #include "gn/track.h"
 #include "gn/track_frame.h"
-
-namespace {
 
 // Streaming copy (m3s_debug_copy): the measured HBM ceiling bench.py reports
 // beside the 8 TB/s spec. 16 B per lane per access (dwordx4), 4 accesses in

@@ -1,4 +1,4 @@
-"""CPU checks of the solver knobs (csrc/m3s_gn.hip: one table row per knob,
+"""CPU checks of the solver knobs (csrc/gn/knobs.h: one table row per knob,
 m3s_set_knob): which names each build of the library knows, that a set returns
 the value before it, that the environment is read, and that a knob set through
 the table reaches the host planner. No GPU needed: the libraries load here as

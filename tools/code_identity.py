@@ -10,7 +10,8 @@ kernel metadata notes (register counts, LDS, scratch, arguments) and the symbol
 tables. The __hip_cuid_<hash> symbol is ignored: hipcc derives it from the
 source path. Prints the first difference, or `identical: <n> functions`; the
 exit status is non-zero on a difference. CPU only. The proof that a change which
-only moves source text (the order rule in csrc/m3s_gn.hip) left the device code
+only moves source text (between csrc/m3s_gn.hip and its parts in csrc/gn/, or
+within the order rule that opens csrc/m3s_gn.hip) left the device code
 alone."""
 import os
 import subprocess

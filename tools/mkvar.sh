@@ -1,11 +1,11 @@
 #!/bin/bash
 # Build a library variant of the current tree: tools/mkvar.sh NAME [-DFLAG=V ...]
 # -> variants/lib_NAME.so (git-ignored; shipped to the GPU box by gpurun).
+# The sources and flags are build()'s own (__graft_entry__.hipcc_cmd).
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift
 mkdir -p "$R/variants"
-C="$R/mast3r-slam-ysh_amd/csrc"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -std=c++17 -fPIC -shared "$@" \
-  -I "$R/include" "$C/m3s_gn.hip" "$C/m3s_match.hip" "$C/m3s_fuse.hip" "$C/m3s_symbolic.cpp" \
-  -o "$R/variants/lib_$name.so"
+cd "$R"
+python -c 'import subprocess, sys, __graft_entry__ as g; subprocess.check_call(g.hipcc_cmd(sys.argv[1], sys.argv[2:]))' \
+  "$R/variants/lib_$name.so" "$@"
