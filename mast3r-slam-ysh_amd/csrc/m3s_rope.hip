@@ -12,16 +12,22 @@
 // frequencies: two loads, 2k rotations, two stores per head) and an
 // element-wise one for everything the vector kernel cannot take (k does not
 // divide Q, a head wider than a wave's 64 lanes, a misaligned base or stride).
-// Both evaluate theta and the rotation by the same two functions below, with
-// FMA contraction off.
+// Both evaluate theta and the rotation by the two functions of
+// m3s_rope_device.h (shared with m3s_attn.hip), with FMA contraction off.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "m3s_gn.h"
 #include "m3s_rope.h"
+#include "m3s_rope_device.h"
 
 namespace {
+
+using m3s_rope::CosSin;
+using m3s_rope::rope_angle;
+using m3s_rope::rope_freq;
+using m3s_rope::rope_rotate;
 
 constexpr int kWave = 64;
 constexpr int kRopeThreads = 256;
@@ -31,31 +37,6 @@ constexpr int64_t kMaxBlocks = 1 << 20;  // the waves stride over the tokens bey
 inline int launch_status() { return hipGetLastError() == hipSuccess ? M3S_OK : M3S_ELAUNCH; }
 
 #pragma clang fp contract(off)
-
-// f0 / base^(i/Q): a rounded i/Q, powf, one division
-__device__ __forceinline__ float rope_freq(int i, int Q, float base, float f0) {
-  const float x = (float)i / (float)Q;
-  return f0 / powf(base, x);
-}
-
-struct CosSin {
-  float c, s;
-};
-
-// one product, then the accurate sincosf (full argument reduction)
-__device__ __forceinline__ CosSin rope_angle(int64_t p, float freq) {
-  const float theta = (float)p * freq;
-  CosSin r;
-  sincosf(theta, &r.s, &r.c);
-  return r;
-}
-
-template <typename T>
-__device__ __forceinline__ void rope_rotate(T &u, T &v, CosSin t) {
-  const float uf = (float)u, vf = (float)v;
-  u = (T)((uf * t.c) - (vf * t.s));
-  v = (T)((vf * t.c) + (uf * t.s));
-}
 
 // lanes_per_head = 2 Q / k <= 64; heads_per_pass = 64 / lanes_per_head; the
 // lanes beyond heads_per_pass * lanes_per_head have nothing to do.

@@ -38,6 +38,11 @@ and for ``RetrievalDatabase(quantizer="device")``.
 MASt3R's attention, in place on the q or k slice of a qkv buffer, one launch;
 ``mast3r_slam_amd.rope`` puts it into a loaded model.
 
+``attention_rope`` (new; include/m3s_attn.h) is the attention core between an
+attention's ``Linear``s: RoPE2D of q and k, scores, softmax and the product
+with v in one launch, fp32, head dimension 64, written in the [B, N, C] layout
+``proj`` takes; ``mast3r_slam_amd.attention`` puts it into a loaded model.
+
 ``head_postprocess`` (new; include/m3s_head.h) is the tail of MASt3R's
 catmlp+dpt head: from the DPT map and the local-feature MLP's output to X, C, D
 and Q in the slots and dtypes ``match_dense``, ``track_frame`` and the factor
@@ -268,6 +273,24 @@ class RopeArgs(ctypes.Structure):
     ]
 
 
+# every symbol include/m3s_attn.h declares
+ATTN_EXPORTS = ("m3s_attn_rope",)
+ATTN_HEAD_DIM = 64
+
+
+class AttnArgs(ctypes.Structure):
+    """Mirror of ``m3s_attn_args`` (include/m3s_attn.h)."""
+
+    _fields_ = [
+        ("q", _VP), ("k", _VP), ("v", _VP), ("out", _VP), ("qpos", _VP), ("kpos", _VP),
+        ("B", ctypes.c_int64), ("Nq", ctypes.c_int64), ("Nk", ctypes.c_int64), ("H", ctypes.c_int64),
+        ("D", ctypes.c_int64),
+        ("q_sb", ctypes.c_int64), ("q_sn", ctypes.c_int64), ("k_sb", ctypes.c_int64), ("k_sn", ctypes.c_int64),
+        ("v_sb", ctypes.c_int64), ("v_sn", ctypes.c_int64), ("o_sb", ctypes.c_int64), ("o_sn", ctypes.c_int64),
+        ("base", ctypes.c_float), ("f0", ctypes.c_float), ("scale", ctypes.c_float), ("dtype", ctypes.c_int),
+    ]
+
+
 # every symbol include/m3s_head.h declares
 HEAD_EXPORTS = ("m3s_head_postprocess",)
 HEAD_F32, HEAD_F16 = 0, 1
@@ -366,6 +389,8 @@ def _load(path=LIB_PATH):
                               "m3s_asmk_quantize": AsmkQuantizeArgs}.get(f, AsmkDb)), _VP]
     lib.m3s_rope_2d.restype = ctypes.c_int  # include/m3s_rope.h
     lib.m3s_rope_2d.argtypes = [P(RopeArgs), _VP]
+    lib.m3s_attn_rope.restype = ctypes.c_int  # include/m3s_attn.h
+    lib.m3s_attn_rope.argtypes = [P(AttnArgs), _VP]
     lib.m3s_head_postprocess.restype = ctypes.c_int  # include/m3s_head.h
     lib.m3s_head_postprocess.argtypes = [P(HeadArgs), _VP]
     return lib
@@ -911,6 +936,101 @@ def rope_2d(tokens, positions, base, f0):
     a.base, a.f0, a.dtype = float(base), float(f0), _ROPE_DTYPES[tokens.dtype]
     _raise(_lib.m3s_rope_2d(ctypes.byref(a), _stream(tokens.device)), "m3s_rope_2d")
     return tokens
+
+
+# ---------------------------------------------------------- attention ---
+def _attn_strides(t, N, row):
+    """(batch, token) element strides of a [B, N, H, D] view; the stride of a
+    dimension of size 1 is arbitrary: give it the dense value."""
+    sn = t.stride(1) if N > 1 else row
+    sb = t.stride(0) if t.shape[0] > 1 else (N - 1) * sn + row
+    return sb, sn
+
+
+def attention_rope(q, k, v, qpos, kpos, base, f0, scale, *, out=None):
+    """The attention core of MASt3R's blocks in one launch (new entry point;
+    m3s_attn_rope; croco models/blocks.py:94-112, 149-169): RoPE2D of q and k
+    (the rotation of ``rope_2d``, bitwise), softmax(scale q' k'^T) v.
+
+    q [B, Nq, H, 64], k and v [B, Nk, H, 64]: float32 views with a contiguous
+    head row and the heads of a token back to back (stride(3) == 1, stride(2)
+    == 64); the token and batch strides are free, so the three slices
+    ``qkv[:, :, i]`` of an attention's [B, N, 3, H, D] buffer and the dense
+    projections of a cross attention are taken as they are. They are only
+    read. qpos [B, Nq, 2], kpos [B, Nk, 2] int64 (y, x), or both None for no
+    rotation.
+
+    -> out [B, Nq, H * 64] float32, the layout ``proj`` takes. out= writes into
+    the caller's tensor: its rows must be contiguous, its token and batch
+    strides are free. On the current stream; no allocation when out is given;
+    no host synchronisation; two runs agree bitwise."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"attention_rope: {name} must be a tensor")
+    # layout and dtype first, the device last, in the order of rope_2d
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be {torch.float32} (got {t.dtype})")
+        if t.dim() != 4:
+            raise RuntimeError(f"{name} must be [B, N, H, D] (got {tuple(t.shape)})")
+    B, Nq, H, D = (int(x) for x in q.shape)
+    if D != ATTN_HEAD_DIM:
+        raise RuntimeError(f"attention_rope: D = {D}, only the head dimension {ATTN_HEAD_DIM} is built")
+    Nk = int(k.shape[1])
+    if tuple(k.shape) != (B, Nk, H, D):
+        raise RuntimeError(f"k must be [{B}, Nk, {H}, {D}] (got {tuple(k.shape)})")
+    if tuple(v.shape) != (B, Nk, H, D):
+        raise RuntimeError(f"v must be [{B}, {Nk}, {H}, {D}] (got {tuple(v.shape)})")
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        if t.numel() and (t.stride(3) != 1 or (H > 1 and t.stride(2) != D)):
+            raise RuntimeError(f"{name}: a head row must be contiguous and the heads of a token back to back "
+                               "(stride(3) == 1, stride(2) == D)")
+    if (qpos is None) != (kpos is None):
+        raise RuntimeError("attention_rope: qpos and kpos must both be given or both be None")
+    for t, name, n in ((qpos, "qpos", Nq), (kpos, "kpos", Nk)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"attention_rope: {name} must be a tensor or None")
+        if t.dtype != torch.int64:
+            raise RuntimeError(f"{name} must be {torch.int64} (got {t.dtype})")
+        if tuple(t.shape) != (B, n, 2):
+            raise RuntimeError(f"{name} must be [{B}, {n}, 2] (got {tuple(t.shape)})")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
+    row = H * D
+    if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise RuntimeError("attention_rope: out must be a tensor")
+        if out.dtype != torch.float32:
+            raise RuntimeError(f"out must be {torch.float32} (got {out.dtype})")
+        if tuple(out.shape) != (B, Nq, row):
+            raise RuntimeError(f"out must be [{B}, {Nq}, {row}] (got {tuple(out.shape)})")
+        if out.numel() and out.stride(2) != 1:
+            raise RuntimeError("out: a row must be contiguous (stride(2) == 1)")
+    if Nk == 0 and B * Nq * H:
+        raise RuntimeError("attention_rope: Nk = 0, a softmax over no keys")
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (qpos, "qpos"), (kpos, "kpos"), (out, "out")):
+        if t is None:
+            continue
+        if t.device.type != "cuda":
+            raise RuntimeError(f"{name} must be on a ROCm device (got {t.device}); no CPU path")
+        if t.device != q.device:
+            raise RuntimeError(f"attention_rope: {name} is on {t.device}, q on {q.device}")
+    if out is None:
+        out = torch.empty((B, Nq, row), dtype=torch.float32, device=q.device)
+    if B * Nq * H == 0:
+        return out
+    a = AttnArgs()
+    a.q, a.k, a.v, a.out, a.qpos, a.kpos = _p(q), _p(k), _p(v), _p(out), _p(qpos), _p(kpos)
+    a.B, a.Nq, a.Nk, a.H, a.D = B, Nq, Nk, H, D
+    a.q_sb, a.q_sn = _attn_strides(q, Nq, row)
+    a.k_sb, a.k_sn = _attn_strides(k, Nk, row)
+    a.v_sb, a.v_sn = _attn_strides(v, Nk, row)
+    a.o_sb, a.o_sn = _attn_strides(out, Nq, row)
+    a.base, a.f0, a.scale, a.dtype = float(base), float(f0), float(scale), ROPE_F32
+    _raise(_lib.m3s_attn_rope(ctypes.byref(a), _stream(q.device)), "m3s_attn_rope")
+    return out
 
 
 # --------------------------------------------------------------- head ---
