@@ -4,8 +4,9 @@
 // upload_plan, gn_prepare_impl (host prepare), finish_plan / host_finish and
 // gn_prepare_async (the prologue launch).
 // Relies on m3s_gn.hip above the include list (Layout / gn_layout,
-// kStageDoubles, kSplitUpdates, the call prologue, S, launch_ok) and on
-// gn/knobs.h; declares set_lds_attributes_once, which gn/iterate.h defines.
+// kStageDoubles, kSplitUpdates), gn/prologue.h (the call prologue), gn/args.h
+// (S, launch_ok) and gn/knobs.h; declares set_lds_attributes_once, which
+// gn/iterate.h defines.
 
 struct PlanMeta {
   int epoch = 0;  // solve launches since m3s_gn_prepare (column-task flags / tickets)

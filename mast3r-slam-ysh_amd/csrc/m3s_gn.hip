@@ -1,17 +1,20 @@
 // m3s_gn.hip — MI355X (gfx950) Gauss-Newton backend and tracker for MASt3R-SLAM.
 //
-// One translation unit: the backend's device code below, section by section,
-// then the host side of the backend (gn/knobs.h, gn/launch.h, gn/plan.h,
-// gn/iterate.h), the tracker (gn/track.h) and the track_frame front end
-// (gn/track_frame.h), then the two debug kernels and the C exports. The gn/*.h
-// files are parts of this file, not stand-alone headers: each is text inside
-// the one anonymous namespace opened below, has no includes or guards of its
-// own, and relies on what stands before it. Every launch is on the caller's
-// stream; a call does not wait for the device except where noted. Sections of
-// this file are named by their rule lines (`// ---- name --`).
+// One translation unit: the backend's device code, section by section, below
+// as far as the dense tail on the f64 MFMA and from there in parts
+// (gn/tail_cyc.h, gn/tail_pair.h, gn/chol_small.h, gn/prologue.h, gn/border.h),
+// then the host side of the backend (gn/args.h, gn/knobs.h, gn/launch.h,
+// gn/plan.h, gn/iterate.h), the tracker (gn/track.h) and the track_frame front
+// end (gn/track_frame.h), then the two debug kernels (gn/debug.h) and the C
+// exports. The gn/*.h files are parts of this file, not
+// stand-alone headers: each is text inside the one anonymous namespace opened
+// below, has no includes or guards of its own, and relies on what stands
+// before it. Every launch is on the caller's stream; a call does not wait for
+// the device except where noted. Sections of this file are named by their rule
+// lines (`// ---- name --`).
 //
 // gauss_newton_{points,rays,calib} (gn_full, gn/iterate.h):
-//   prepare    gn_prologue_kernel (call prologue): ranks the edge ids, writes the
+//   prepare    gn_prologue_kernel (gn/prologue.h): ranks the edge ids, writes the
 //              linearize edge order, flags, info, dx; the ids go to pinned memory
 //              and the host builds (or fetches from the plan cache) the symbolic
 //              plan while the first linearize runs (gn/plan.h). Above 2048
@@ -30,13 +33,12 @@
 //                else, up to 512 columns (large graphs), over the chip:
 //                  assemble_slots_kernel (block-sparse LLT),
 //                  df_factor_kernel (wave-level dataflow factorisation),
-//                  tail_pair_kernel when the plan has a dense tail (under the
-//                  bare rule inside the section "dense tail over many
-//                  workgroups", "Round 5"; from 32 tail columns its extra
-//                  workgroups run the sparse back-substitution, gcol_worker),
+//                  tail_pair_kernel (gn/tail_pair.h) when the plan has a dense
+//                  tail (from 32 tail columns its extra workgroups run the
+//                  sparse back-substitution, gcol_worker, gn/tail_pair.h),
 //                  else col_backsub_kernel (dataflow)
 //                else: sparse_llt_kernel<0>, in two phases around border_kernel
-//                  (border kernel) and tail_llt_kernel (dense tail on the f64
+//                  (gn/border.h) and tail_llt_kernel (dense tail on the f64
 //                  MFMA) with a dense tail
 //                no sparse plan that fits: edge_reduce_kernel (gathering launch),
 //                  assemble_kernel and the tiled dense Cholesky (assemble)
@@ -50,13 +52,15 @@
 //   track_prep_kernel, track_prep_count_kernel, then the tracker's launches.
 // The test build (-DM3S_TEST_PATHS) adds the A/B reference paths behind the
 // test-only knobs (gn/knobs.h): col_factor_kernel (column tasks),
-// chol_small_kernel (small dense Cholesky), tail_cyc_kernel, the VGPR-staged
-// gathering kernel.
+// chol_small_kernel (gn/chol_small.h), tail_cyc_kernel (gn/tail_cyc.h), the
+// VGPR-staged gathering kernel.
+// m3s_debug_copy / m3s_debug_sim3: hbm_copy_kernel, sim3_debug_kernel
+// (gn/debug.h).
 //
 // Order rule: the sections below and then the include list are the order of
-// the device code. Device functions and kernels keep their relative order, in
-// this file and inside a part, and the first host mention of each kernel
-// template keeps its place (gn/launch.h, gn/plan.h, gn/iterate.h; it decides
+// the device code. The parts keep their places in the list, device functions
+// and kernels keep their relative order, in this file and inside a part, and
+// the first host mention of each kernel template keeps its place (gn/launch.h, gn/plan.h, gn/iterate.h; it decides
 // where the instantiation lands). The code object holds real calls to
 // non-inlined device functions, so a reordering changes pc-relative literals
 // and the device code can no longer be compared instruction for instruction
@@ -3502,1433 +3506,19 @@ __global__ void __launch_bounds__(64 * kTailNW, 1) tail_llt_kernel(TailArgs A) {
 #undef M3S_STAMP
 }
 
-// ----------------------------- dense tail over many workgroups (default) --
-// The same left-looking 16x16-tile factorisation as tail_llt_kernel, with
-// tile column J on workgroup J (TC workgroups of 4 waves, wave w holding the
-// rows I = J + w (mod 4) in MFMA accumulator registers). Workgroup J applies
-// the update of every finished column k < J as soon as column k is published
-// (A(I,J)^T -= L(J,k) L(I,k)^T, k ascending: the single-workgroup kernel's
-// order, so the result is bitwise the same), then factors its diagonal tile,
-// forms its panel L(I,J)^T = W_J A(I,J)^T, and publishes the panel, W_J and
-// y'_J (write-through stores drained before an epoch flag). The critical
-// path per tile column is one hand-off + one tile update + the diagonal
-// factor, instead of the whole left-looking sweep of one CU (281 us at 256
-// KFs). The last workgroup then runs the back-substitution L^T x = y' over
-// the published tiles (sc1 loads).
-struct TailSync {
-  int32_t *tflag;    // [TC] epoch flags: tile column published (W_J, y'_J, the LgT tiles: back-substitution)
-  int epoch;
-  double *ypg;     // y' of every tile column [16 TC]
-  double *LgT;     // the L tiles again, L(I,J) (not transposed) in the MFMA C layout, [tile][2][64 lanes][2] (back-substitution A operands)
-  double *LgG;     // the L tiles as tagged granules, [tile][4][64 lanes] x {double, epoch tag, 0} (16 B; zeroed per call)
-  int warm;        // 1: warm the diagonal factor's code on a dummy tile first (tail_diag_warm)
-};
-constexpr size_t kTailGranBytes = (size_t)kTailMaxT * (kTailMaxT + 1) / 2 * 64 * 4 * 16;
-
-__device__ __forceinline__ f64x4 ld_sc1_f64x4(const double *p) {
-  f64x4 v;
-#pragma unroll
-  for (int r = 0; r < 4; r++) v[r] = ld_sc1(p + r);
-  return v;
-}
-__device__ __forceinline__ void st_sc1_f64x4(double *p, f64x4 v) {
-#pragma unroll
-  for (int r = 0; r < 4; r++) st_sc1(p + r, v[r]);
-}
-
-// Tagged-granule tile hand-off (MI355X_MICROARCH.md, handoff-1to1 / R2): each
-// entry is one 16-B write-through store {value, epoch tag}, read back by a
-// 16-B sc1 buffer load; the consumer checks the tags, so there is no flag, no
-// producer drain and no second round trip (flag, then payload).
-struct GranTile {
-  u32x4 v[4];
-};
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gran_rsrc(double *p) {
-  return __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)kTailGranBytes, 0x00020000);
-}
-__device__ __forceinline__ void gran_load(__amdgpu_buffer_rsrc_t R, int tile, int lane, GranTile &g) {
-#pragma unroll
-  for (int r = 0; r < 4; r++) g.v[r] = poll_b128(R, ((tile * 4 + r) * 64 + lane) * 16);
-}
-__device__ __forceinline__ bool gran_ready(const GranTile &g, int want) {  // wave-uniform
-  const bool ok = g.v[0].z == (unsigned)want && g.v[1].z == (unsigned)want && g.v[2].z == (unsigned)want &&
-                  g.v[3].z == (unsigned)want;
-  return __ballot(!ok) == 0;
-}
-__device__ __forceinline__ f64x4 gran_val(const GranTile &g) {
-  f64x4 d;
-#pragma unroll
-  for (int r = 0; r < 4; r++) d[r] = __longlong_as_double((long long)(((unsigned long long)g.v[r].y << 32) | g.v[r].x));
-  return d;
-}
-// Granule r of every lane of a tile is one 1-KB run ([tile][4][64 lanes]):
-// each 16-B store / load instruction of the wave covers whole lines (round 4;
-// lane-major [tile][64][4] made every instruction a 25 %-dense 4-KB stride of
-// partial-line write-through stores)
-__device__ __forceinline__ void gran_store(__amdgpu_buffer_rsrc_t R, int tile, int lane, f64x4 d, int want) {
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(d[r]);
-    const u32x4 w = {(unsigned)(b & 0xffffffffu), (unsigned)(b >> 32), (unsigned)want, 0u};
-    __builtin_amdgcn_raw_buffer_store_b128(w, R, ((tile * 4 + r) * 64 + lane) * 16, 0, 16);
-  }
-}
-
-// The last workgroup of a tail launch: back-substitution L^T x = y' over the
-// published tiles (after every column flag), x of the tail columns to A.rhs.
-__device__ __forceinline__ void tail_backsub_wg(const TailArgs &A, const TailSync &S, double *yv, double *xv) {
-  const int n = 7 * A.nc;
-  const int TC = (n + 15) / 16;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int lr = lane & 15, lk = lane >> 4;
-  const int want = S.epoch + 1;
-  double *Wg = A.Wg;
-  // The last workgroup: back-substitution L^T x = y' over the published tiles
-  // (every column k < J was waited for above). Wave w owns the tile rows
-  // J' = w (mod 4) of y' (it alone updates them); x_K is formed by the owner
-  // of row K as soon as its own updates from x_{K+1..} are in, then handed to
-  // the other waves through LDS with a flag: no workgroup barrier per step.
-  // The same sums in the same order as tail_llt_kernel's loop.
-  __shared__ int xflag[kTailMaxT];
-  if (wave == 0) {  // every column's W, y' and LgT tiles are out (column flags, one per lane)
-    int spins = 0;
-    while (__ballot(lane < TC && __hip_atomic_load(S.tflag + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != want)) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > kColSpins) {
-        if (lane == 0) __hip_atomic_store(A.flags + kFlagSplitFail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-    }
-  }
-  __syncthreads();
-  if (tid == 0) M3S_CSTAMP(2, 698, 0);
-  // every W_K^T to LDS (rows padded to 17: conflict-free column reads)
-  __shared__ double WlT[kTailMaxT * 16 * 17];
-  {  // all loads in flight at once (16-B sc1 buffer loads; out of range past TC reads zeros)
-    constexpr int kWL = kTailMaxT * 256 / (2 * 64 * kTailNW);
-    const __amdgpu_buffer_rsrc_t RW = __builtin_amdgcn_make_buffer_rsrc(Wg, 0, kTailMaxT * 256 * 8, 0x00020000);
-    u32x4 wv[kWL];
-#pragma unroll
-    for (int i = 0; i < kWL; i++) {
-      const int q2 = 2 * (tid + 64 * kTailNW * i);
-      wv[i] = __builtin_amdgcn_raw_buffer_load_b128(RW, q2 < 256 * TC ? q2 * 8 : 0x7fffff00, 0, 16);
-    }
-    double yl[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const int q = tid + 64 * kTailNW * i;
-      yl[i] = q < 16 * TC ? ld_sc1(S.ypg + q) : 0.0;
-    }
-#pragma unroll
-    for (int i = 0; i < kWL; i++) {
-      const int q2 = 2 * (tid + 64 * kTailNW * i);
-      WlT[(q2 >> 4) * 17 + (q2 & 15)] = __longlong_as_double((long long)(((unsigned long long)wv[i].y << 32) | wv[i].x));
-      WlT[(q2 >> 4) * 17 + (q2 & 15) + 1] =
-          __longlong_as_double((long long)(((unsigned long long)wv[i].w << 32) | wv[i].z));
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const int q = tid + 64 * kTailNW * i;
-      if (q < 16 * TC) yv[q] = yl[i];
-    }
-  }
-  for (int q = tid; q < 16 * kTailMaxT; q += 64 * kTailNW) xv[q] = 0.0;
-  if (tid < kTailMaxT) xflag[tid] = 0;
-  __syncthreads();
-  // y_J -= L(K, J)^T x_K from the LgT tile (operand order: 32 B per lane).
-  // The operands of the next step are in flight while this one runs: every
-  // load is a 16-B sc1 buffer load issued unconditionally (rows a step does
-  // not need read out of range, which returns zeros without a memory access),
-  // so each step issues the same number of loads and the compiler waits for
-  // exactly the older step's (24 per wave, two steps = 48 < the 63 vmcnt).
-  // Per step K the owner of row K - 1 applies x_K to that row first and forms
-  // x_{K-1} at once (the chain per step is one tile update + one 16-term
-  // dot product), then applies x_K to its other rows. Each row still takes
-  // its updates in decreasing K (the same sums).
-  constexpr int kTW = (kTailMaxT + kTailNW - 1) / kTailNW;  // tile rows J' of one wave
-  constexpr int kRing = 3;
-  const __amdgpu_buffer_rsrc_t RT =
-      __builtin_amdgcn_make_buffer_rsrc(S.LgT, 0, kTailMaxT * (kTailMaxT + 1) / 2 * 256 * 8, 0x00020000);
-  constexpr int kFar = 0x7fffff00;  // out of range
-  f64x4 lt[kRing][kTW];
-  auto ld2 = [&](int off, double &x0, double &x1) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(RT, off, 0, 16);
-    x0 = __longlong_as_double((long long)(((unsigned long long)v.y << 32) | v.x));
-    x1 = __longlong_as_double((long long)(((unsigned long long)v.w << 32) | v.z));
-  };
-  auto bs_load = [&](int K, int slot) {
-#pragma unroll
-    for (int t = 0; t < kTW; t++) {
-      const int Jc = wave + kTailNW * t;
-      // tile layout [tile][2 halves][64 lanes][2 doubles] (every 16-B access of
-      // the wave covers whole lines)
-      const bool in = K >= 0 && Jc < K;
-      const int off = in ? (tail_tile(K, Jc) * 256 + 2 * lane) * 8 : kFar;
-      double x0, x1, x2, x3;
-      ld2(off, x0, x1);
-      ld2(in ? off + 1024 : kFar, x2, x3);
-      lt[slot][t] = f64x4{x0, x1, x2, x3};
-    }
-  };
-  auto form_x = [&](int K) {  // the owner of row K, all of whose updates are in
-    const int jv = min(16, n - 16 * K);
-    // x_K[r] = sum_i W_K^T[r][i] y'_K[i]: lane r + 16 g sums i in [4 g, 4 g + 4),
-    // then the four groups by the permlane swaps (4 dependent FMAs + 2 swap
-    // steps on the chain instead of 16 FMAs, round 5)
-    if (lane < 16) {
-      double x = 0.0;
-#pragma unroll
-      for (int i = 0; i < 16; i++) x += WlT[(K * 16 + lane) * 17 + i] * yv[16 * K + i];
-      xv[16 * K + lane] = lane < jv ? x : 0.0;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) __hip_atomic_store(xflag + K, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (lane == 0) M3S_CSTAMP(2, 700 + K, 0);
-  };
-#pragma unroll
-  for (int d = 0; d < kRing; d++) bs_load(TC - 1 - d, d);
-  if (tid == 0) M3S_CSTAMP(2, 699, 0);
-  if ((TC - 1) % kTailNW == wave) form_x(TC - 1);
-  for (int K0 = TC - 1; K0 >= 0; K0 -= kRing) {
-#pragma unroll
-    for (int d = 0; d < kRing; d++) {
-      const int K = K0 - d;
-      if (K >= 0) {
-        if (K % kTailNW != wave) {  // (the owner formed x_K itself, in the step before)
-          int spins = 0;
-          while (__hip_atomic_load(xflag + K, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0 &&
-                 spins < (1 << 22))
-            spins++;
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        }
-        double xb[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) xb[q] = xv[16 * K + 4 * q + lk];
-#pragma unroll
-        for (int pass = 0; pass < 2; pass++) {
-#pragma unroll
-          for (int t = 0; t < kTW; t++) {
-            const int Jc = wave + kTailNW * t;
-            if (pass == 0 ? Jc == K - 1 : Jc < K - 1) {
-              // (L^T x)[m], m = lr: lane l holds L(K,Jc)^T[lr][lk + 4q]; the 4 lanes of
-              // one m add their partial sums (VALU: the MFMA form spent 15/16 of its work
-              // on copies of x)
-              double u = 0.0;
-#pragma unroll
-              for (int q = 0; q < 4; q++) u += lt[d][t][q] * xb[q];
-              u = sum_xor16_32(u);
-              if (lane < 16) yv[16 * Jc + lane] -= u;
-              if (pass == 0) {
-                wave_lds_fence();  // row K - 1's y' before this wave reads it
-                form_x(K - 1);
-              }
-            }
-          }
-        }
-        wave_lds_fence();
-      }
-      bs_load(K - kRing, d);
-    }
-  }
-  __syncthreads();  // every x_K
-  for (int j = tid; j < n; j += 64 * kTailNW) A.rhs[7 * A.c0 + j] = xv[j];
-  if (tid == 0) M3S_CSTAMP(2, 511, 0);
-}
-
-
-// Round 2: the L tiles go from workgroup to workgroup as tagged granules
-// (one hop = one store + one polled load), the panel follows the updates
-// without a workgroup barrier (waves 1..3 wait for W_J on an LDS flag), and
-// the column flag only guards what the back-substitution reads.
-__global__ void __launch_bounds__(64 * kTailNW, 1) tail_cyc_kernel(TailArgs A, TailSync S) {
-  if (A.flags[kFlagStop]) return;
-  __shared__ double Wk[16][17];
-  __shared__ double yv[16 * kTailMaxT], xv[16 * kTailMaxT];
-  __shared__ int fail_s, wready;
-  const int n = 7 * A.nc;
-  const TailSrc TS = tail_src(A, n);
-  const int TC = (n + 15) / 16, TR = (n + 16) / 16;
-  const int In = n / 16, rn = n - 16 * In;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int lr = lane & 15, lk = lane >> 4;
-  const int J = blockIdx.x;
-  const int want = S.epoch + 1;
-  double *Wg = A.Wg;
-  const __amdgpu_buffer_rsrc_t R = gran_rsrc(S.LgG);
-  // rows: wave 0 holds only the diagonal tile (its factor is the critical
-  // path), waves 1..3 the rows below it, I = J + w + 3 u
-  constexpr int kRC = (kTailMaxT + 2) / 3;
-  auto rowI = [&](int u) { return wave == 0 ? (u == 0 ? J : -1) : J + wave + 3 * u; };
-  auto live = [&](int u) {
-    const int I = rowI(u);
-    return I >= 0 && I < TR;
-  };
-  if (tid == 0) fail_s = 0, wready = 0;
-  for (int q = tid; q < 16 * kTailMaxT; q += 64 * kTailNW) yv[q] = 0.0;
-  __syncthreads();
-  f64x4 acc[kRC];
-#pragma unroll
-  for (int u = 0; u < kRC; u++) {
-    f64x4 v = {0.0, 0.0, 0.0, 0.0};
-    if (live(u)) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) v[r] = tail_entry(A, TS, n, 16 * rowI(u) + lr, 16 * J + lk + 4 * r);
-    }
-    acc[u] = v;
-  }
-  // updates from the finished columns, k ascending (the single-workgroup
-  // kernel's order: bitwise the same sums), each tile as soon as it lands
-  auto poll_tile = [&](int t, GranTile &g) {
-    int spins = 0;
-    for (;;) {
-      gran_load(R, t, lane, g);
-      if (gran_ready(g, want)) break;
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > kColSpins) {
-        if (lane == 0) fail_s = 1;
-        break;
-      }
-    }
-  };
-  if (wave == 0 && J > 0 && S.warm) tail_diag_warm(Wk, xv + 16 * J, min(16, n - 16 * J), In == J ? rn : -1, lane);
-  f64x4 rk_last = {0.0, 0.0, 0.0, 0.0};  // tile L(J, J-1): waves 1..3 apply column J - 1 row by row below
-  for (int k = 0; k < J; k++) {
-    GranTile gk;
-    poll_tile(tail_tile(J, k), gk);
-    const f64x4 rk = gran_val(gk);
-    if (wave == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; q++) acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(-rk[q], rk[q], acc[0], 0, 0, 0);
-    } else if (k + 1 == J) {
-      rk_last = rk;
-    } else {
-      // every row's tile of column k: all loads in flight at once, the rows
-      // that have landed are applied, the rest polled again
-      unsigned pend = 0;
-#pragma unroll
-      for (int u = 0; u < kRC; u++)
-        if (live(u)) pend |= 1u << u;
-      int spins = 0;
-      while (pend) {
-        GranTile g[kRC];
-#pragma unroll
-        for (int u = 0; u < kRC; u++)
-          if (pend & (1u << u)) gran_load(R, tail_tile(rowI(u), k), lane, g[u]);
-#pragma unroll
-        for (int u = 0; u < kRC; u++) {
-          if ((pend & (1u << u)) && gran_ready(g[u], want)) {
-            const f64x4 ri = gran_val(g[u]);
-#pragma unroll
-            for (int q = 0; q < 4; q++) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(-rk[q], ri[q], acc[u], 0, 0, 0);
-            pend &= ~(1u << u);
-          }
-        }
-        if (pend) {
-          __builtin_amdgcn_s_sleep(1);
-          if (++spins > kColSpins) {
-            if (lane == 0) fail_s = 1;
-            break;
-          }
-        }
-      }
-    }
-  }
-  if (wave == 0) {  // the diagonal tile: factor, W_J
-    if (tid == 0) M3S_CSTAMP(2, J, 1);
-    if (tid == 0) M3S_CSTAMP(2, 600 + J, 0);
-    if (tail_diag_mfma(acc[0], Wk, yv + 16 * J, min(16, n - 16 * J), In == J ? rn : -1, lane) && lane == 0)
-      fail_s = 1;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // Wk (and y') before the flag
-    if (lane == 0) __hip_atomic_store(&wready, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (tid == 0) M3S_CSTAMP(2, J, 2);
-    // W^T ([16][16] row-major, element e = 16 l + r holds W[r][l]): four
-    // stores of 64 consecutive elements, whole lines each
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int e = 64 * i + lane;
-      st_sc1(Wg + (size_t)J * 256 + e, Wk[e & 15][e >> 4]);
-    }
-    if (In == J && lane < 16) st_sc1(S.ypg + 16 * J + lane, yv[16 * J + lane]);
-  } else {
-    // row by row, the sub-diagonal tile first: the update from column J - 1
-    // (as its tile lands), then the panel tile L(I, J)^T = W_J A(I, J)^T,
-    // handed off as granules at once
-    bool have_w = false;
-#pragma unroll
-    for (int u = 0; u < kRC; u++) {
-      const int I = rowI(u);
-      if (live(u)) {
-        if (J > 0) {
-          GranTile g;
-          poll_tile(tail_tile(I, J - 1), g);
-          const f64x4 ri = gran_val(g);
-#pragma unroll
-          for (int q = 0; q < 4; q++) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(-rk_last[q], ri[q], acc[u], 0, 0, 0);
-        }
-        if (!have_w) {
-          int spins = 0;
-          while (__hip_atomic_load(&wready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0 &&
-                 spins < (1 << 20)) {
-            __builtin_amdgcn_s_sleep(1);
-            spins++;
-          }
-          if (spins >= (1 << 20) && lane == 0) fail_s = 1;
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-          have_w = true;
-        }
-        f64x4 d = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int q = 0; q < 4; q++) d = __builtin_amdgcn_mfma_f64_16x16x4f64(Wk[lr][4 * q + lk], acc[u][q], d, 0, 0, 0);
-        gran_store(R, tail_tile(I, J), lane, d, want);
-        if (I == J + 1 && tid == 64) M3S_CSTAMP(2, J, 0);
-        if (I == In && lr == rn) {  // y' of this column from the RHS row
-#pragma unroll
-          for (int r = 0; r < 4; r++) st_sc1(S.ypg + 16 * J + lk + 4 * r, d[r]);
-        }
-      }
-    }
-    // L(I, J) itself (operands swapped: A(I, J) W^T) for the back-substitution,
-    // after every hand-off of this wave (16-B write-through stores)
-    const __amdgpu_buffer_rsrc_t RT =
-        __builtin_amdgcn_make_buffer_rsrc(S.LgT, 0, kTailMaxT * (kTailMaxT + 1) / 2 * 256 * 8, 0x00020000);
-#pragma unroll
-    for (int u = 0; u < kRC; u++) {
-      const int I = rowI(u);
-      if (live(u) && I < TC) {
-        f64x4 dt = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int q = 0; q < 4; q++) dt = __builtin_amdgcn_mfma_f64_16x16x4f64(acc[u][q], Wk[lr][4 * q + lk], dt, 0, 0, 0);
-        const unsigned long long b0 = __double_as_longlong(dt[0]), b1 = __double_as_longlong(dt[1]),
-                                 b2 = __double_as_longlong(dt[2]), b3 = __double_as_longlong(dt[3]);
-        const u32x4 w0 = {(unsigned)b0, (unsigned)(b0 >> 32), (unsigned)b1, (unsigned)(b1 >> 32)};
-        const u32x4 w1 = {(unsigned)b2, (unsigned)(b2 >> 32), (unsigned)b3, (unsigned)(b3 >> 32)};
-        const int off = (tail_tile(I, J) * 256 + 2 * lane) * 8;  // (halves of 1 KB: whole lines per store)
-        __builtin_amdgcn_raw_buffer_store_b128(w0, RT, off, 0, 16);
-        __builtin_amdgcn_raw_buffer_store_b128(w1, RT, off + 1024, 0, 16);
-      }
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every store of this wave has left
-  __syncthreads();
-  if (tid == 0) {
-    if (fail_s) __hip_atomic_store(A.flags + kFlagSplitFail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(S.tflag + J, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    M3S_CSTAMP(2, J, 3);
-  }
-  if (J != TC - 1) return;
-  tail_backsub_wg(A, S, yv, xv);
-}
-
-
-// Round 4: two tile columns per workgroup (J0 = 2 b, J1 = J0 + 1). The
-// chain per tile column of tail_cyc_kernel is a hand-off (~1.3 us) + the
-// diagonal factor (~2.4 us) + a panel tile; here the second column of a pair
-// takes its sub-diagonal panel tile L(J1, J0) and the update of its diagonal
-// from the first column inside the workgroup (wave 0, no hand-off), so the
-// chain has one hand-off per two columns. Wave 0 holds the tiles (J0, J0),
-// (J1, J0), (J1, J1); waves 1..3 the rows below, I = J1 + w + 3 u, for both
-// columns. Per tile the same updates in the same order as tail_cyc_kernel
-// (columns k ascending, then the pair's own first column): bitwise the same
-// factor; the back-substitution is the same code (tail_backsub_wg).
-// RC: row tiles per wave (waves 1..3 hold rows J1 + w + 3 u, u < RC): 7 up to
-// 23 tile rows (the register arrays of 11 spill), 11 up to kTailMaxT
-// ------------------------------------------------------------------------
-// Round 5: the sparse back-substitution off the critical path. The sparse
-// columns' x is affine in the tail's: x_s = L_ss^-T (y_s - L_ts^T x_t), so
-// for every sparse column k
-//   X_k = [a_k | B_k] = W_k^T (R_k - sum_{i sparse in struct(k)} L_ik^T X_i),
-//   R_k = [y_k | 0] - sum_{i tail in struct(k)} L_ik^T [0 | E_i]
-// (E_i picks x_i out of x_t), and x_k = a_k + B_k x_t. The X_k recursion
-// needs only the factor, so extra workgroups of the dense tail's launch run
-// it (column tasks in reverse level order, the X_i of the sparse ancestors
-// by epoch flags) while the tail factors on its own workgroups; once the
-// tail's x_t is out, x_k = a_k + B_k x_t is one short dot product per entry
-// and col_backsub_kernel's chain of dependent hand-offs (9 levels, ~27 us,
-// plus its launch at 256 KFs) leaves the critical path. x_k differs from the
-// substitution by fp64 round-off (a different summation order).
-struct GArgs {
-  double *X;     // [m][7][nx] row-major per column (nx = 1 + 7 nc, padded)
-  int nx, n_pairs;
-  int32_t *task, *comb, *fin, *xt_ready;  // ticket / ticket / counter / flag words (colsync; zeroed per call)
-  int32_t *cnt;                           // [m] chunks of X_k done (colsync; zeroed per call)
-};
-constexpr int kGBat = 8;    // sparse ancestors' X_i loads in flight per lane
-constexpr int kGCapS = 24;  // sparse ancestors' L_ik staged in LDS per wave (the rest read from global)
-constexpr int kGMaxS = 512; // sparse ancestors of one column: < m <= 512 on the chip-wide path
-constexpr int kGTmap = kTailMaxT * 16 / 7 + 8;
-#ifndef M3S_GSLEEP
-#define M3S_GSLEEP 8
-#endif
-__device__ __forceinline__ bool g_poll(const int32_t *flag, int want) {  // bounded wait for one epoch flag
-  for (int spins = 0; __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != want; spins++) {
-    if (spins > kColSpins) return false;
-    __builtin_amdgcn_s_sleep(M3S_GSLEEP);
-  }
-  return true;
-}
-// wait_flags with the workers' poll interval (they wait beside the tail's hand-offs)
-__device__ __forceinline__ bool g_wait_flags(const int32_t *flag, const int32_t *idx, int q0, int q1, int lim, int want,
-                                             int lane) {
-  int spins = 0;
-  for (int qb = q0; qb < q1; qb += 64) {
-    const int q = qb + lane;
-    const int i = q < q1 ? idx[q] : -1;
-    for (;;) {
-      const bool ok = i < 0 || i >= lim ||
-                      __hip_atomic_load(flag + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == want;
-      if (__ballot(!ok) == 0) break;
-      __builtin_amdgcn_s_sleep(M3S_GSLEEP);
-      if (++spins > kColSpins) return false;
-    }
-  }
-  return true;
-}
-// Per wave, task (k, ch): the 64 columns c = 64 ch + lane of X_k (a column of
-// ~300 c at 256 KFs is ~170 KB of X_i reads: one CU's fabric bandwidth made a
-// whole-column task ~10 us, so a column is spread over S = nx / 64 waves on
-// as many CUs); the last of its S chunks to finish (per-column counter
-// G.cnt, epoch-based) publishes done2[k].
-__device__ void gcol_worker(const ColArgs &C, const GArgs &G) {
-  __shared__ double Lw[kTailNW][kGCapS * 49], Ww[kTailNW][49];
-  __shared__ int tmapw[kTailNW][kGTmap];  // tail block (i - c0) -> its position q in struct(k), or -1
-  __shared__ int sqw[kTailNW][kGMaxS];    // the sparse ancestors' positions q in struct(k), list order
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int32_t *pl = C.plan;
-  const int32_t *col_ptr = pl + C.off[1], *col_row = pl + C.off[2], *col_slot = pl + C.off[3],
-                *corder = pl + C.off[29];
-  const int want = C.epoch + 1, c0 = C.c0, nct = C.m - c0, nx = G.nx, nt = 7 * nct;
-  const int nG = (int)gridDim.x - G.n_pairs;
-  const int S = (nx + 63) / 64;
-  double *Lk = Lw[wave], *Wk = Ww[wave];
-  int *tmap = tmapw[wave], *sq = sqw[wave];
-  // 1. the X_k recursion, column chunks in reverse level order
-  const int base = C.epoch * (C.ncols * S + kTailNW * nG);
-  for (;;) {
-    const int t = wave_gticket(G.task) - base;
-    if (t >= C.ncols * S) break;
-    const int ci = t / S, ch = t - S * ci;
-    const int k = corder[C.ncols - 1 - ci];
-    const int q0 = col_ptr[k], q1 = col_ptr[k + 1];
-    if (lane == 0 && ch == 0) M3S_CSTAMP(1, k, 0);
-    for (int q = lane; q < nct; q += 64) tmap[q] = -1;
-    wave_lds_fence();
-    int ns = 0;
-    for (int qb = q0; qb < q1; qb += 64) {  // tail positions; sparse ancestors compacted in list order
-      const int q = qb + lane;
-      const int i = q < q1 ? col_row[q] : c0;
-      if (q < q1 && i >= c0) tmap[i - c0] = q - q0;
-      const uint64_t sm = __ballot(q < q1 && i < c0);
-      const int pos = ns + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
-      if (q < q1 && i < c0 && pos < kGMaxS) sq[pos] = q - q0;
-      ns += __popcll(sm);
-    }
-    ns = min(ns, kGMaxS);
-    wave_lds_fence();
-    // the factor is final: the ancestors' L_ik and W_k by plain loads
-    for (int e = lane; e < 49 * min(ns, kGCapS); e += 64) Lk[e] = C.L[(size_t)col_slot[q0 + sq[e / 49]] * 49 + e % 49];
-    if (lane < 49) Wk[lane] = C.Dinv[(size_t)k * 49 + lane];
-    const int c = 64 * ch + lane;
-    const bool cv = c < nx;
-    double r[7];
-    {  // R_k: [y_k | 0] minus, for the tail block i holding dof j = c - 1, row j of L_ik^T
-      const int j = c - 1;
-      const int q = c > 0 && j < nt ? tmap[j / 7] : -1;
-      const double *Lq = C.L + (size_t)col_slot[q0 + (q >= 0 ? q : 0)] * 49 + (j % 7) * 7;
-#pragma unroll
-      for (int a = 0; a < 7; a++) r[a] = (c == 0 ? C.y[(size_t)k * 7 + a] : 0.0) - (q >= 0 ? Lq[a] : 0.0);
-    }
-    if (!g_wait_flags(C.done2, col_row, q0, q1, c0, want, lane) && lane == 0) set_fail(C.flags);  // sparse ancestors' X_i
-    wave_lds_fence();
-    if (lane == 0 && ch == 0) M3S_CSTAMP(1, k, 1);
-    const int cl = cv ? c : 0;
-    for (int u0 = 0; u0 < ns; u0 += kGBat) {  // - L_ik^T X_i, ancestors in list order
-      double xi[kGBat][7];
-#pragma unroll
-      for (int v = 0; v < kGBat; v++) {
-        const double *Xi = G.X + (size_t)col_row[q0 + sq[min(u0 + v, ns - 1)]] * 7 * nx + cl;
-#pragma unroll
-        for (int b = 0; b < 7; b++) xi[v][b] = ld_sc1(Xi + (size_t)b * nx);
-      }
-#pragma unroll
-      for (int v = 0; v < kGBat; v++) {
-        const int u = u0 + v;
-        if (u >= ns) break;
-        const double *Lq = u < kGCapS ? Lk + 49 * u : C.L + (size_t)col_slot[q0 + sq[u]] * 49;
-#pragma unroll
-        for (int a = 0; a < 7; a++) {
-          double sm = 0.0;
-#pragma unroll
-          for (int b = 0; b < 7; b++) sm += Lq[b * 7 + a] * xi[v][b];
-          r[a] -= sm;
-        }
-      }
-    }
-    double *Xk = G.X + (size_t)k * 7 * nx;
-    if (cv) {
-#pragma unroll
-      for (int a = 0; a < 7; a++) {  // X_k = W_k^T r
-        double x = 0.0;
-#pragma unroll
-        for (int b = 0; b < 7; b++) x += Wk[b * 7 + a] * r[b];
-        st_sc1(Xk + (size_t)a * nx + c, x);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this chunk's X_k stores have left
-    if (lane == 0) {
-      const int o = __hip_atomic_fetch_add(G.cnt + k, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (o == want * S - 1) {  // the column's last chunk
-        __hip_atomic_store(C.done2 + k, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        M3S_CSTAMP(1, k, 2);
-      }
-    }
-    wave_lds_fence();  // before the next task rewrites this wave's LDS
-  }
-  // 2. x_k = a_k + B_k x_t: one column per wave over every worker wave; B_k
-  // is in registers (ready once X_k is) before the tail's x_t is out, so
-  // after its flag only x_t is read (one round trip) and summed
-  const int cbase = C.epoch * (C.ncols + kTailNW * nG);
-  constexpr int kCU = 16 * kTailMaxT / 64;  // tail dofs per lane (nt < 16 kTailMaxT)
-  int ri;
-  bool rv;
-  xred_index<7>(lane, ri, rv);
-  for (;;) {
-    const int t = wave_gticket(G.comb) - cbase;
-    if (t >= C.ncols) break;
-    const int k = corder[C.ncols - 1 - t];  // root side first: those X_k are out first
-    const double *Xk = G.X + (size_t)k * 7 * nx;
-    if (lane == 0 && !g_poll(C.done2 + k, want)) set_fail(C.flags);  // X_k of another workgroup
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    double bx[kCU][7];
-#pragma unroll
-    for (int u = 0; u < kCU; u++) {
-      const int j = lane + 64 * u;
-#pragma unroll
-      for (int a = 0; a < 7; a++) bx[u][a] = j < nt ? ld_sc1(Xk + (size_t)a * nx + 1 + j) : 0.0;
-    }
-    const double a0 = ld_sc1(Xk + (size_t)(rv ? ri : 0) * nx);  // a_k[ri]: this lane's row of the result
-    if (lane == 0 && !g_poll(G.xt_ready, want)) set_fail(C.flags);  // the tail's x_t
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    double acc[7];
-#pragma unroll
-    for (int a = 0; a < 7; a++) acc[a] = 0.0;
-#pragma unroll
-    for (int u = 0; u < kCU; u++) {
-      const int j = lane + 64 * u;
-      const double xt = j < nt ? ld_sc1(C.y + (size_t)7 * c0 + j) : 0.0;
-#pragma unroll
-      for (int a = 0; a < 7; a++) acc[a] += bx[u][a] * xt;
-    }
-    // the 7 wave sums by the transposed reduction (permlane swaps + DPP):
-    // lane ri-holder ends with row ri's sum
-    const double v = xreduceN_dpp<7>(acc, lane);
-    if (rv) st_sc1(C.y + (size_t)k * 7 + ri, a0 + v);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // x_k (and any failure flag) out before the ticket
-    if (lane == 0) M3S_CSTAMP(1, k, 3);
-    const int f = wave_gticket(G.fin);  // the wave that combines the last column finishes the step
-    if (f - C.epoch * C.ncols == C.ncols - 1) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      col_finish(C, lane);
-    }
-  }
-}
-
-template <int RC>
-__global__ void __launch_bounds__(64 * kTailNW, 1) tail_pair_kernel(TailArgs A, TailSync S, ColArgs C, GArgs G) {
-  if (A.flags[kFlagStop]) return;
-  if (G.X && (int)blockIdx.x >= G.n_pairs) {  // the sparse back-substitution's workers
-    gcol_worker(C, G);
-    return;
-  }
-  __shared__ double Wk[2][16][17];
-  __shared__ double yv[16 * kTailMaxT], xv[16 * kTailMaxT];
-  __shared__ f64x4 Lsub[64];  // L(J1, J0) in operand order (waves 1..3 update their J1 tiles with it)
-  __shared__ int fail_s, wready[2], lready;
-  const int n = 7 * A.nc;
-  const TailSrc TS = tail_src(A, n);
-  const int TC = (n + 15) / 16, TR = (n + 16) / 16;
-  const int In = n / 16, rn = n - 16 * In;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int lr = lane & 15, lk = lane >> 4;
-  const int J0 = 2 * (int)blockIdx.x, jn = min(2, TC - J0), J1 = J0 + 1, Jl = J0 + jn - 1;
-  const int want = S.epoch + 1;
-  double *Wg = A.Wg;
-  const __amdgpu_buffer_rsrc_t R = gran_rsrc(S.LgG);
-  constexpr int kRC = RC;
-  auto rowI = [&](int u) { return wave == 0 ? (u < jn ? J0 + u : -1) : Jl + wave + 3 * u; };
-  auto live = [&](int u) {
-    const int I = rowI(u);
-    return I >= 0 && I < TR;
-  };
-  if (tid == 0) fail_s = 0, wready[0] = 0, wready[1] = 0, lready = 0;
-  for (int q = tid; q < 16 * kTailMaxT; q += 64 * kTailNW) yv[q] = 0.0;
-  __syncthreads();
-  // acc0[u]: tile (I, J0)^T; acc1[u]: tile (I, J1)^T (rows I >= J1)
-  f64x4 acc0[kRC], acc1[kRC];
-#pragma unroll
-  for (int u = 0; u < kRC; u++) {
-    f64x4 v0 = {0.0, 0.0, 0.0, 0.0}, v1 = {0.0, 0.0, 0.0, 0.0};
-    if (live(u)) {
-      const int I = rowI(u);
-#pragma unroll
-      for (int r = 0; r < 4; r++) v0[r] = tail_entry(A, TS, n, 16 * I + lr, 16 * J0 + lk + 4 * r);
-      if (jn == 2 && I >= J1) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) v1[r] = tail_entry(A, TS, n, 16 * I + lr, 16 * J1 + lk + 4 * r);
-      }
-    }
-    acc0[u] = v0;
-    acc1[u] = v1;
-  }
-  auto poll_tile = [&](int t, GranTile &g) {
-    int spins = 0;
-    for (;;) {
-      gran_load(R, t, lane, g);
-      if (gran_ready(g, want)) break;
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > kColSpins) {
-        if (lane == 0) fail_s = 1;
-        break;
-      }
-    }
-  };
-  auto mma = [&](f64x4 &acc, const f64x4 &key, const f64x4 &ri) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-key[q], ri[q], acc, 0, 0, 0);
-  };
-  if (wave == 0 && J0 > 0 && S.warm)
-    tail_diag_warm(Wk[0], xv + 16 * J0, min(16, n - 16 * J0), In == J0 ? rn : -1, lane);
-  f64x4 rk0_last = {0.0, 0.0, 0.0, 0.0}, rk1_last = {0.0, 0.0, 0.0, 0.0};
-  for (int k = 0; k < J0; k++) {
-    // the pair's two key tiles L(J0, k), L(J1, k): both loads in flight, one poll
-    GranTile g0, g1;
-    {
-      int spins = 0;
-      for (;;) {
-        gran_load(R, tail_tile(J0, k), lane, g0);
-        if (jn == 2) gran_load(R, tail_tile(J1, k), lane, g1);
-        if (gran_ready(g0, want) && (jn < 2 || gran_ready(g1, want))) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > kColSpins) {
-          if (lane == 0) fail_s = 1;
-          break;
-        }
-      }
-    }
-    const f64x4 rk0 = gran_val(g0);
-    f64x4 rk1 = {0.0, 0.0, 0.0, 0.0};
-    if (jn == 2) rk1 = gran_val(g1);
-    if (wave == 0) {
-      mma(acc0[0], rk0, rk0);
-      if (jn == 2) {
-        mma(acc0[1], rk0, rk1);
-        mma(acc1[1], rk1, rk1);
-      }
-    } else if (k + 1 == J0) {
-      rk0_last = rk0, rk1_last = rk1;
-    } else {
-      unsigned pend = 0;
-#pragma unroll
-      for (int u = 0; u < kRC; u++)
-        if (live(u)) pend |= 1u << u;
-      int spins = 0;
-      while (pend) {
-        GranTile g[kRC];
-#pragma unroll
-        for (int u = 0; u < kRC; u++)
-          if (pend & (1u << u)) gran_load(R, tail_tile(rowI(u), k), lane, g[u]);
-#pragma unroll
-        for (int u = 0; u < kRC; u++) {
-          if ((pend & (1u << u)) && gran_ready(g[u], want)) {
-            const f64x4 ri = gran_val(g[u]);
-            mma(acc0[u], rk0, ri);
-            if (jn == 2) mma(acc1[u], rk1, ri);
-            pend &= ~(1u << u);
-          }
-        }
-        if (pend) {
-          __builtin_amdgcn_s_sleep(1);
-          if (++spins > kColSpins) {
-            if (lane == 0) fail_s = 1;
-            break;
-          }
-        }
-      }
-    }
-  }
-  const __amdgpu_buffer_rsrc_t RT =
-      __builtin_amdgcn_make_buffer_rsrc(S.LgT, 0, kTailMaxT * (kTailMaxT + 1) / 2 * 256 * 8, 0x00020000);
-  // L(I, J) itself (A(I, J) W^T: operands swapped) for the back-substitution
-  auto store_lgt = [&](int I, int J, const f64x4 &a, int slot) {
-    f64x4 dt = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int q = 0; q < 4; q++) dt = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], Wk[slot][lr][4 * q + lk], dt, 0, 0, 0);
-    const unsigned long long b0 = __double_as_longlong(dt[0]), b1 = __double_as_longlong(dt[1]),
-                             b2 = __double_as_longlong(dt[2]), b3 = __double_as_longlong(dt[3]);
-    const u32x4 w0 = {(unsigned)b0, (unsigned)(b0 >> 32), (unsigned)b1, (unsigned)(b1 >> 32)};
-    const u32x4 w1 = {(unsigned)b2, (unsigned)(b2 >> 32), (unsigned)b3, (unsigned)(b3 >> 32)};
-    const int off = (tail_tile(I, J) * 256 + 2 * lane) * 8;  // (halves of 1 KB: whole lines per store)
-    __builtin_amdgcn_raw_buffer_store_b128(w0, RT, off, 0, 16);
-    __builtin_amdgcn_raw_buffer_store_b128(w1, RT, off + 1024, 0, 16);
-  };
-  auto panel = [&](const f64x4 &a, int slot) {  // L(I, J)^T = W_J A(I, J)^T, operand order
-    f64x4 d = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int q = 0; q < 4; q++) d = __builtin_amdgcn_mfma_f64_16x16x4f64(Wk[slot][lr][4 * q + lk], a[q], d, 0, 0, 0);
-    return d;
-  };
-  auto wait_lds = [&](int *f) {
-    int spins = 0;
-    while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0 && spins < (1 << 20)) {
-      __builtin_amdgcn_s_sleep(1);
-      spins++;
-    }
-    if (spins >= (1 << 20) && lane == 0) fail_s = 1;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  };
-  if (wave == 0) {
-    // diagonal J0, then (jn == 2) the pair's sub-diagonal tile, the second
-    // diagonal's update from it, the second diagonal
-    if (tid == 0) M3S_CSTAMP(2, J0, 1);
-    if (tid == 0) M3S_CSTAMP(2, 600 + J0, 0);
-    if (tail_diag_mfma(acc0[0], Wk[0], yv + 16 * J0, min(16, n - 16 * J0), In == J0 ? rn : -1, lane) && lane == 0)
-      fail_s = 1;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) __hip_atomic_store(&wready[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (tid == 0) M3S_CSTAMP(2, J0, 2);
-    if (jn == 2) {
-      const f64x4 d = panel(acc0[1], 0);  // L(J1, J0)^T
-      Lsub[lane] = d;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      if (lane == 0) __hip_atomic_store(&lready, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (J1 == In && lr == rn) {  // y' of column J0 from the RHS row
-#pragma unroll
-        for (int r = 0; r < 4; r++) st_sc1(S.ypg + 16 * J0 + lk + 4 * r, d[r]);
-      }
-      mma(acc1[1], d, d);
-      if (tid == 0) M3S_CSTAMP(2, J1, 1);
-      if (tid == 0) M3S_CSTAMP(2, 600 + J1, 0);
-      if (tail_diag_mfma(acc1[1], Wk[1], yv + 16 * J1, min(16, n - 16 * J1), In == J1 ? rn : -1, lane) && lane == 0)
-        fail_s = 1;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      if (lane == 0) __hip_atomic_store(&wready[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (tid == 0) M3S_CSTAMP(2, J1, 2);
-    }
-    // W^T of each column ([16][16] row-major: element e = 16 l + r holds
-    // W[r][l]): four stores of 64 consecutive elements, whole lines each
-    // (lane l storing its row of 16 was 16 partial-line write-through stores)
-#pragma unroll
-    for (int j = 0; j < jn; j++) {
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int e = 64 * i + lane;
-        st_sc1(Wg + (size_t)(J0 + j) * 256 + e, Wk[j][e & 15][e >> 4]);
-      }
-      if (In == J0 + j && lane < 16) st_sc1(S.ypg + 16 * (J0 + j) + lane, yv[16 * (J0 + j) + lane]);
-    }
-    if (jn == 2) store_lgt(J1, J0, acc0[1], 0);
-  } else {
-    // The wave's first row first, on its own (in waves 1 and 2 it carries
-    // the next pair's chain: its two tiles go out before any other work):
-    // the deferred update from column J0 - 1 as its tile lands, the panel
-    // tile L(I, J0), the update of (I, J1) from the pair's first column
-    // (L(J1, J0) from wave 0), the panel tile L(I, J1), each handed off at
-    // once. Then the other rows phase by phase, every row's MFMA chain of a
-    // phase interleaved with the others' (one row at a time left each
-    // row's ~12 dependent MFMAs and stores exposed: ~1.5 us per row,
-    // profiles/r04/tail_stamps_pair_rows_fine.txt). Per tile the same
-    // updates in the same order.
-    if (lane == 0) M3S_CSTAMP(2, 1000 + 16 * J0 + 15, wave);
-    auto deferred = [&](int u) {
-      GranTile g;
-      poll_tile(tail_tile(rowI(u), J0 - 1), g);
-      const f64x4 ri = gran_val(g);
-      mma(acc0[u], rk0_last, ri);
-      if (jn == 2) mma(acc1[u], rk1_last, ri);
-    };
-    auto put_y = [&](int I, int J, const f64x4 &d) {  // y' of column J from the RHS row
-      if (I == In && lr == rn) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) st_sc1(S.ypg + 16 * J + lk + 4 * r, d[r]);
-      }
-    };
-    f64x4 ls = {0.0, 0.0, 0.0, 0.0};
-    if (live(0)) {
-      const int I = rowI(0);
-      if (J0 > 0) deferred(0);
-      if (tid == 64) M3S_CSTAMP(2, 1300 + 16 * J0, 0);
-      wait_lds(&wready[0]);
-      const f64x4 d0 = panel(acc0[0], 0);
-      gran_store(R, tail_tile(I, J0), lane, d0, want);
-      if (tid == 64) M3S_CSTAMP(2, 1300 + 16 * J0, 1);
-      put_y(I, J0, d0);
-      if (jn == 2) {
-        wait_lds(&lready);
-        ls = Lsub[lane];
-        mma(acc1[0], ls, d0);
-        wait_lds(&wready[1]);
-        const f64x4 d = panel(acc1[0], 1);
-        gran_store(R, tail_tile(I, J1), lane, d, want);
-        if (tid == 64) M3S_CSTAMP(2, 1300 + 16 * J0, 3);
-        if (I == J1 + 1 && tid == 64) M3S_CSTAMP(2, J1, 0);
-        put_y(I, J1, d);
-      }
-      if (lane == 0) M3S_CSTAMP(2, 1000 + 16 * J0, wave);
-    }
-    if (live(1)) {  // (rows are dealt in order: live(1) implies live(0))
-      // the deferred update: every remaining row's tile in flight at once,
-      // applied as they land
-      if (J0 > 0) {
-        unsigned pend = 0;
-#pragma unroll
-        for (int u = 1; u < kRC; u++)
-          if (live(u)) pend |= 1u << u;
-        int spins = 0;
-        while (pend) {
-          GranTile g[kRC];
-#pragma unroll
-          for (int u = 1; u < kRC; u++)
-            if (pend & (1u << u)) gran_load(R, tail_tile(rowI(u), J0 - 1), lane, g[u]);
-#pragma unroll
-          for (int u = 1; u < kRC; u++) {
-            if ((pend & (1u << u)) && gran_ready(g[u], want)) {
-              const f64x4 ri = gran_val(g[u]);
-              mma(acc0[u], rk0_last, ri);
-              if (jn == 2) mma(acc1[u], rk1_last, ri);
-              pend &= ~(1u << u);
-            }
-          }
-          if (pend) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > kColSpins) {
-              if (lane == 0) fail_s = 1;
-              break;
-            }
-          }
-        }
-      }
-      if (tid == 64) M3S_CSTAMP(2, 1300 + 16 * J0 + 1, 0);
-      // (a wave whose row 0 is dead has no rows at all, so the flags below
-      // were already seen by row 0)
-      f64x4 d0[kRC];
-#pragma unroll
-      for (int u = 1; u < kRC; u++) {
-        d0[u] = f64x4{0.0, 0.0, 0.0, 0.0};
-        if (live(u)) d0[u] = panel(acc0[u], 0);
-      }
-#pragma unroll
-      for (int u = 1; u < kRC; u++)
-        if (live(u)) {
-          gran_store(R, tail_tile(rowI(u), J0), lane, d0[u], want);
-          put_y(rowI(u), J0, d0[u]);
-        }
-      if (tid == 64) M3S_CSTAMP(2, 1300 + 16 * J0 + 1, 1);
-      if (jn == 2) {
-#pragma unroll
-        for (int u = 1; u < kRC; u++)
-          if (live(u)) mma(acc1[u], ls, d0[u]);
-        f64x4 d1[kRC];
-#pragma unroll
-        for (int u = 1; u < kRC; u++) {
-          d1[u] = f64x4{0.0, 0.0, 0.0, 0.0};
-          if (live(u)) d1[u] = panel(acc1[u], 1);
-        }
-#pragma unroll
-        for (int u = 1; u < kRC; u++)
-          if (live(u)) {
-            gran_store(R, tail_tile(rowI(u), J1), lane, d1[u], want);
-            put_y(rowI(u), J1, d1[u]);
-          }
-        if (tid == 64) M3S_CSTAMP(2, 1300 + 16 * J0 + 1, 3);
-      }
-      if (lane == 0) M3S_CSTAMP(2, 1000 + 16 * J0 + 1, wave);
-    }
-    // the L tiles for the back-substitution, after every hand-off
-#pragma unroll
-    for (int u = 0; u < kRC; u++) {
-      const int I = rowI(u);
-      if (live(u) && I < TC) {
-        store_lgt(I, J0, acc0[u], 0);
-        if (jn == 2) store_lgt(I, J1, acc1[u], 1);
-      }
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every store of this wave has left
-  __syncthreads();
-  if (tid == 0) {
-    if (fail_s) {  // out before the column flags (the back-substitution workers may finish the step early)
-      __hip_atomic_store(A.flags + kFlagSplitFail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    for (int j = 0; j < jn; j++) __hip_atomic_store(S.tflag + J0 + j, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int j = 0; j < jn; j++) M3S_CSTAMP(2, J0 + j, 3);
-  }
-  if ((int)blockIdx.x != (G.X ? G.n_pairs : (int)gridDim.x) - 1) return;
-  tail_backsub_wg(A, S, yv, xv);
-  if (G.X) {  // x_t is out (plain stores): release, then the workers combine
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave
-    __syncthreads();
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(G.xt_ready, S.epoch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-#ifdef M3S_TEST_PATHS  // reached only through the dense knob: every graph it fits (m <= 31) has a sparse plan
-// ------------------------------------------------- small dense Cholesky --
-// Thread (tr, tc) of a 16 x 32 grid owns A[lr*16 + tr][lc*32 + tc]. The RHS g
-// is appended as row n, so the factor's row n is y = L^-1 g. After the loop
-// the registers hold L (lower triangle). NBC = column blocks of 32.
-template <int NBC>
-__global__ void __launch_bounds__(kCholThreads) chol_small_kernel(
-    const double *__restrict__ Aug, int64_t ld, int n, float *__restrict__ Twc, int64_t N,
-    float *__restrict__ dx_out, int32_t *__restrict__ info, int32_t *__restrict__ stop,
-    float delta_thresh) {
-  constexpr int NBR = 2 * NBC;
-  if (*stop) return;
-  const int tid = threadIdx.x;
-  const int tr = tid >> 5, tc = tid & 31;
-  __shared__ double colbuf[2][32 * NBC];
-  __shared__ double xbuf[32 * NBC];
-  __shared__ double ybuf[32 * NBC];
-  __shared__ double red[16][33];
-  __shared__ double dblk[32][33];
-  __shared__ float dxs[32 * NBC];
-  __shared__ float nrm[kCholThreads / 64];
-
-  double A[NBR][NBC];
-#pragma unroll
-  for (int lr = 0; lr < NBR; lr++)
-#pragma unroll
-    for (int lc = 0; lc < NBC; lc++) {
-      const int i = lr * 16 + tr, j = lc * 32 + tc;
-      A[lr][lc] = (i <= n && j < n) ? Aug[(size_t)i * ld + j] : ((i == j) ? 1.0 : 0.0);
-    }
-  for (int k = tid; k < 32 * NBC; k += kCholThreads) xbuf[k] = 0.0, ybuf[k] = 0.0;
-  bool failed = false;
-  int step = 0;
-
-#pragma unroll
-  for (int kb = 0; kb < NBC; kb++) {
-    for (int c = 0; c < 32; c++) {
-      const int k = kb * 32 + c;
-      if (k >= n || failed) break;
-      double *cb = colbuf[step & 1];
-      // owners of column k publish it (rows < k as 0)
-      if (tc == c) {
-#pragma unroll
-        for (int lr = 0; lr < NBR; lr++) {
-          const int i = lr * 16 + tr;
-          cb[i] = (i >= k) ? A[lr][kb] : 0.0;
-        }
-      }
-      __syncthreads();
-      const double d = cb[k];
-      if (!(d > 0.0)) {  // Eigen LLT: non-positive pivot -> failure (dx = 0)
-        failed = true;
-        break;
-      }
-      const double inv = 1.0 / sqrt(d);
-      double lj[NBC];
-#pragma unroll
-      for (int lc = 0; lc < NBC; lc++) lj[lc] = (lc >= kb) ? cb[lc * 32 + tc] * inv : 0.0;
-#pragma unroll
-      for (int lr = 2 * kb; lr < NBR; lr++) {
-        const double li = cb[lr * 16 + tr] * inv;
-#pragma unroll
-        for (int lc = kb; lc < NBC; lc++)
-          if (lc * 32 <= lr * 16 + 15) A[lr][lc] -= li * lj[lc];
-        if (tc == c) A[lr][kb] = li;  // column k of L
-      }
-      step++;
-    }
-  }
-
-  if (failed) {  // every thread saw the same pivot
-    fail_step(n, dx_out, info, stop, delta_thresh);
-    return;
-  }
-
-  // y = row n of the factor
-#pragma unroll
-  for (int lr = 0; lr < NBR; lr++)
-    if (lr * 16 + tr == n)
-#pragma unroll
-      for (int lc = 0; lc < NBC; lc++) {
-        const int j = lc * 32 + tc;
-        if (j < n) ybuf[j] = A[lr][lc];
-      }
-  __syncthreads();
-
-  // back-substitution L^T x = y, 32-column blocks from the bottom
-#pragma unroll
-  for (int kb = NBC - 1; kb >= 0; kb--) {
-    double s = 0.0;
-#pragma unroll
-    for (int lr = 0; lr < NBR; lr++)
-      if (lr * 16 >= (kb + 1) * 32) s += A[lr][kb] * xbuf[lr * 16 + tr];
-    red[tr][tc] = s;
-#pragma unroll
-    for (int lr = 2 * kb; lr < 2 * kb + 2; lr++) dblk[lr * 16 + tr - kb * 32][tc] = A[lr][kb];
-    __syncthreads();
-    if (tid < 64) {
-      const int cc = tid & 31;
-      double rhs = 0.0;
-      if (tid < 32) {
-        const int j = kb * 32 + cc;
-        double acc = 0.0;
-        for (int q = 0; q < 16; q++) acc += red[q][cc];
-        rhs = (j < n) ? ybuf[j] - acc : 0.0;
-      }
-      double x = 0.0;
-      for (int cp = 31; cp >= 0; cp--) {
-        const double xc = __shfl(rhs, cp, 64) / dblk[cp][cp];
-        if (kb * 32 + cp >= n) continue;  // uniform
-        if (cc < cp) rhs -= dblk[cp][cc] * xc;
-        if (cc == cp) x = xc;
-      }
-      if (tid < 32) {
-        const int j = kb * 32 + cc;
-        xbuf[j] = (j < n) ? x : 0.0;
-      }
-    }
-    __syncthreads();
-  }
-  finish_step(xbuf, dxs, nrm, n, Twc, N, dx_out, info, stop, delta_thresh);
-}
-#endif  // M3S_TEST_PATHS (chol_small_kernel)
-
-// ------------------------------------------------------ call prologue --
-// The per-call setup of a GN call on the device, so the call's first
-// linearize can be enqueued right behind it and nothing waits for the host:
-// the edge ids are ranked (the reference's torch::_unique(cat(ii, jj), sorted,
-// return_inverse), gn_kernels.cu:1154-1160) by a bitonic sort of the 2E ids in
-// LDS, the ranks and the linearize edge order (edges grouped by KF j,
-// block_task; the order inside a KF bucket is free: partials are indexed by
-// task, so the sums do not depend on it) go to the workspace, flags / edge
-// counters / info /
-// dx_out are initialised, and ii, jj, K are copied into pinned host memory
-// for the host's symbolic analysis, which then runs while the first linearize
-// kernel does (host_finish).
-constexpr int kProThreads = 1024;
-constexpr int kProMaxE = 2048;  // 2E ids sorted in LDS; larger edge sets take the host path
-static_assert(kProMaxE % kProThreads == 0, "prologue: whole edges per thread");
-struct ProArgs {
-  const int64_t *ii, *jj;
-  const float *K;      // calib: 3x3 (else null)
-  int64_t *down_ii, *down_jj;
-  float *down_K;       // host-mapped pinned copies
-  int E, N, P2;        // P2: power of two >= 2E
-  int32_t *flags, *rank_i, *rank_j, *eorder, *info;
-  uint32_t *edge_cnt;
-  float *dx_out;
-  int n_dx;
-};
-
-// exclusive prefix of one int per thread over the block; *total = block sum
-__device__ int block_excl_scan(int v, int *wsum, int *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int acc = 0;
-    for (int w = 0; w < nw; w++) {
-      const int t = wsum[w];
-      wsum[w] = acc;
-      acc += t;
-    }
-    wsum[16] = acc;
-  }
-  __syncthreads();
-  const int r = wsum[wave] + x - v;
-  *total = wsum[16];
-  __syncthreads();
-  return r;
-}
-
-// minimum and maximum of one int64 pair per thread over the block (every
-// thread gets both)
-__device__ void block_minmax_i64(int64_t &lo, int64_t &hi, int64_t *red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const int64_t a = __shfl_xor(lo, o, 64), b = __shfl_xor(hi, o, 64);
-    lo = a < lo ? a : lo, hi = b > hi ? b : hi;
-  }
-  if (lane == 0) red[wave] = lo, red[16 + wave] = hi;
-  __syncthreads();
-  lo = red[0], hi = red[16];
-  for (int w = 1; w < nw; w++) lo = red[w] < lo ? red[w] : lo, hi = red[16 + w] > hi ? red[16 + w] : hi;
-  __syncthreads();
-}
-
-__device__ __forceinline__ int lower_bound_i64(const int64_t *u, int n, int64_t v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (u[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__global__ void __launch_bounds__(kProThreads) gn_prologue_kernel(ProArgs A) {
-  extern __shared__ __attribute__((aligned(16))) int64_t pro_smem[];
-  __shared__ int wsum[17];
-  __shared__ int64_t red64[32];
-  const int E = A.E, P2 = A.P2, tid = threadIdx.x;
-  constexpr int64_t kPad = 0x7fffffffffffffffLL;
-  int64_t *keys = pro_smem, *uniq = keys + P2;
-  int32_t *cnt = reinterpret_cast<int32_t *>(uniq + P2);  // [P2]: KF bucket counts, then offsets
-  int32_t *erj = cnt + P2;  // [E]
-  // this thread's edges e = tid, tid + 1024 (E <= kProMaxE): their ids stay in registers
-  constexpr int kPer = kProMaxE / kProThreads;
-  int64_t ei[kPer], ej[kPer];
-#pragma unroll
-  for (int u = 0; u < kPer; u++) {
-    const int e = tid + u * kProThreads;
-    ei[u] = e < E ? A.ii[e] : 0, ej[u] = e < E ? A.jj[e] : 0;
-  }
-  int64_t lo = kPad, hi = -kPad - 1;  // id range (keyframe ids: small non-negative integers in practice)
-#pragma unroll
-  for (int u = 0; u < kPer; u++) {
-    const int e = tid + u * kProThreads;
-    if (e < E) {
-      A.down_ii[e] = ei[u], A.down_jj[e] = ej[u];
-      keys[e] = ei[u], keys[E + e] = ej[u];
-      lo = ei[u] < lo ? ei[u] : lo, hi = ei[u] > hi ? ei[u] : hi;
-      lo = ej[u] < lo ? ej[u] : lo, hi = ej[u] > hi ? ej[u] : hi;
-    }
-  }
-  for (int q = 2 * E + tid; q < P2; q += kProThreads) keys[q] = kPad;
-  if (A.K && tid < 9) A.down_K[tid] = A.K[tid];
-  for (int q = tid; q <= E; q += kProThreads) A.edge_cnt[q] = 0u;
-  for (int q = tid; q < A.n_dx; q += kProThreads) A.dx_out[q] = 0.0f;
-  if (tid < 64) A.flags[tid] = 0;
-  block_minmax_i64(lo, hi, red64);  // threads without edges hold (max, min): neutral
-  // bitmap of 64 P2 bits in the uniq region (P2 int64), its word prefix in the keys region
-  int nu = 0;
-  if (E > 0 && (uint64_t)hi - (uint64_t)lo < (uint64_t)64 * P2) {
-    // rank = number of distinct ids below: a presence bitmap over [lo, hi] and
-    // a prefix of its word popcounts (4 barriers instead of the sort's
-    // log2(P2)(log2(P2)+1)/2)
-    uint32_t *bm = reinterpret_cast<uint32_t *>(uniq);
-    int32_t *pre = reinterpret_cast<int32_t *>(keys);
-    const int nwu = (int)(((uint64_t)hi - (uint64_t)lo) >> 5) + 1;
-    for (int q = tid; q < nwu; q += kProThreads) bm[q] = 0u;
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kPer; u++) {
-      if (tid + u * kProThreads < E) {
-        const uint64_t di = (uint64_t)ei[u] - (uint64_t)lo, dj = (uint64_t)ej[u] - (uint64_t)lo;
-        atomicOr(&bm[di >> 5], 1u << (di & 31));
-        atomicOr(&bm[dj >> 5], 1u << (dj & 31));
-      }
-    }
-    __syncthreads();
-    const int segw = (nwu + kProThreads - 1) / kProThreads;
-    int pc = 0;
-    for (int q = 0; q < segw; q++) {
-      const int w = tid * segw + q;
-      pc += w < nwu ? __builtin_popcount(bm[w]) : 0;
-    }
-    int off0 = block_excl_scan(pc, wsum, &nu);
-    for (int q = 0; q < segw; q++) {
-      const int w = tid * segw + q;
-      if (w < nwu) pre[w] = off0, off0 += __builtin_popcount(bm[w]);
-    }
-    __syncthreads();
-    auto rank = [&](int64_t v) {
-      const uint64_t d = (uint64_t)v - (uint64_t)lo;
-      return pre[d >> 5] + __builtin_popcount(bm[d >> 5] & ((1u << (d & 31)) - 1u));
-    };
-#pragma unroll
-    for (int u = 0; u < kPer; u++) {
-      const int e = tid + u * kProThreads;
-      if (e < E) {
-        const int ri = rank(ei[u]), rj = rank(ej[u]);
-        A.rank_i[e] = ri, A.rank_j[e] = rj;
-        erj[e] = rj;
-      }
-    }
-  } else {
-    __syncthreads();
-    for (int k = 2; k <= P2; k <<= 1)  // bitonic sort, ascending
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int i = tid; i < P2; i += kProThreads) {
-          const int l = i ^ j;
-          if (l > i) {
-            const int64_t x = keys[i], y = keys[l];
-            if ((x > y) == ((i & k) == 0)) keys[i] = y, keys[l] = x;
-          }
-        }
-        __syncthreads();
-      }
-    // the sorted unique ids, in order (each thread a run of <= 4 sorted keys)
-    const int seg = (P2 + kProThreads - 1) / kProThreads;
-    auto first = [&](int i) { return i < P2 && keys[i] != kPad && (i == 0 || keys[i] != keys[i - 1]); };
-    int nf = 0;
-    for (int q = 0; q < seg; q++) nf += first(tid * seg + q) ? 1 : 0;
-    int at_ = block_excl_scan(nf, wsum, &nu);
-    for (int q = 0; q < seg; q++)
-      if (first(tid * seg + q)) uniq[at_++] = keys[tid * seg + q];
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kPer; u++) {
-      const int e = tid + u * kProThreads;
-      if (e < E) {
-        const int ri = lower_bound_i64(uniq, nu, ei[u]), rj = lower_bound_i64(uniq, nu, ej[u]);
-        A.rank_i[e] = ri, A.rank_j[e] = rj;
-        erj[e] = rj;
-      }
-    }
-  }
-  const bool bad = nu > A.N;
-  if (tid < 8) A.info[tid] = tid == M3S_INFO_N_UNIQUE ? nu : (tid == M3S_INFO_BAD_EDGE && bad) ? 1 : 0;
-  if (tid == 0 && bad) A.flags[kFlagStop] = 1;  // every launch of the call is a no-op
-  if (bad || E == 0) return;                     // (uniform)
-  for (int q = tid; q < nu; q += kProThreads) cnt[q] = 0;
-  __syncthreads();
-  for (int e = tid; e < E; e += kProThreads) atomicAdd(&cnt[erj[e]], 1);
-  __syncthreads();
-  const int segn = (nu + kProThreads - 1) / kProThreads;  // <= 4
-  int cl[4] = {0, 0, 0, 0}, sum = 0;
-  for (int q = 0; q < segn; q++) {
-    const int i = tid * segn + q;
-    cl[q] = i < nu ? cnt[i] : 0;
-    sum += cl[q];
-  }
-  int tot = 0;
-  int off = block_excl_scan(sum, wsum, &tot);
-  for (int q = 0; q < segn; q++) {
-    const int i = tid * segn + q;
-    if (i < nu) cnt[i] = off, off += cl[q];
-  }
-  __syncthreads();
-  for (int e = tid; e < E; e += kProThreads) A.eorder[atomicAdd(&cnt[erj[e]], 1)] = e;
-}
-inline size_t prologue_lds(int E, int P2) {
-  return sizeof(int64_t) * 2 * (size_t)P2 + sizeof(int32_t) * ((size_t)P2 + (size_t)E);
-}
-inline int prologue_p2(int64_t E) {
-  int p = 2;
-  while (p < 2 * E) p <<= 1;
-  return p;
-}
-
-// ------------------------------------------------------- border kernel --
-// Dense-tail border updates spread over the chip (global factors, between
-// sparse_llt_kernel phases 1 and 2): one task per wave, 4 waves per
-// workgroup, y in global memory (D.rhs, written by phase 1). The tasks are
-// independent; in the single-workgroup kernel they took ~290 us at N = 256.
-// The kernel stays at this position, behind the prologue, to keep the device
-// code's order (top of the file); a later change may move it next to the tail.
-constexpr int kBorderWaves = 4;
-__global__ void __launch_bounds__(64 * kBorderWaves) border_kernel(SparseDev D) {
-  if (D.flags[kFlagStop]) return;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int32_t *pl = D.plan;
-  const int32_t *clq = pl + D.off[28];
-  const int nc = clq[0], c0 = clq[1], nt0 = nc * (nc + 1) / 2;
-  const int r = lane / 7, c = lane % 7;
-  const bool act49 = lane < 49;
-  const int lane49 = act49 ? lane : 0, r7 = act49 ? r * 7 : 0, c7 = act49 ? c * 7 : 0;
-  const int lane7 = lane < 7 ? lane : 0;
-  double *stg = smem + (size_t)wave * kStageDoubles;
-  double *y = const_cast<double *>(D.rhs);
-  for (int t = blockIdx.x * kBorderWaves + wave; t < nt0; t += gridDim.x * kBorderWaves)
-    border_task<true>(t, nc, c0, pl, D.off, D.L, y, r7, c7, lane49, lane, lane7, act49, stg, D.tail_A, D.tail_ld);
-}
-
-// ---------------------------------------------------------------- host --
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
-int launch_ok() { return hipGetLastError() == hipSuccess ? M3S_OK : M3S_ELAUNCH; }
-
-ResidualParams make_params(const m3s_gn_args *a) {
-  ResidualParams P;
-  P.inv_sig_a = a->sigma_a != 0.0f ? (float)(1.0 / (double)a->sigma_a) : 0.0f;
-  P.inv_sig_b = a->sigma_b != 0.0f ? (float)(1.0 / (double)a->sigma_b) : 0.0f;
-  P.C_thresh = a->C_thresh;
-  P.Q_thresh = a->Q_thresh;
-  P.fx = P.fy = P.cx = P.cy = 0.0f;
-  P.width = a->width;
-  P.height = a->height;
-  P.border = (float)a->pixel_border;
-  P.z_eps = a->z_eps;
-  P.huber_k = 1.345f;  // hard-coded in the reference kernels (gn_kernels.cu:172-175)
-  return P;
-}
-
-int check_args(const m3s_gn_args *a) {
-  if (!a || !a->Twc || !a->Xs || !a->Cs || !a->ii || !a->jj || !a->idx_ii2jj || !a->valid_match ||
-      !a->Q || !a->info || !a->workspace)
-    return M3S_EINVAL;
-  if (a->N < 1 || a->HW < 1 || a->E < 0) return M3S_EINVAL;
-  if (a->mode == M3S_MODE_CALIB && (!a->K || a->width < 1 || a->height < 1)) return M3S_EINVAL;
-  if (a->workspace_bytes < gn_layout(a->N, a->HW, a->E).total) return M3S_EINVAL;
-  if (a->HW * 3 >= ((int64_t)1 << 40)) return M3S_ETOOLARGE;
-  if (a->mode < 0 || a->mode > 2) return M3S_EINVAL;
-  return M3S_OK;
-}
-
+#include "gn/tail_cyc.h"
+#include "gn/tail_pair.h"
+#include "gn/chol_small.h"
+#include "gn/prologue.h"
+#include "gn/border.h"
+#include "gn/args.h"
 #include "gn/knobs.h"
 #include "gn/launch.h"
 #include "gn/plan.h"
 #include "gn/iterate.h"
 #include "gn/track.h"
 #include "gn/track_frame.h"
-
-// Streaming copy (m3s_debug_copy): the measured HBM ceiling bench.py reports
-// beside the 8 TB/s spec. 16 B per lane per access (dwordx4), 4 accesses in
-// flight per lane, non-temporal loads and stores, grid-stride over the buffer.
-__global__ void __launch_bounds__(256) hbm_copy_kernel(const f32x4 *__restrict__ src, f32x4 *__restrict__ dst,
-                                                       int64_t n4) {
-  const int64_t stride = (int64_t)gridDim.x * 256 * 4;
-  for (int64_t base = (int64_t)blockIdx.x * 256 * 4 + threadIdx.x; base < n4; base += stride) {
-    f32x4 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (base + 256 * k < n4) v[k] = __builtin_nontemporal_load(src + base + 256 * k);
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (base + 256 * k < n4) __builtin_nontemporal_store(v[k], dst + base + 256 * k);
-  }
-}
-
-// Sim(3) device helpers on arrays (m3s_debug_sim3): the functions the hot path
-// applies, run as-is for the property tests of tests/test_gpu_sim3.py
-__global__ void sim3_debug_kernel(int op, const float *__restrict__ a, const float *__restrict__ b,
-                                  float *__restrict__ out, int64_t n) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  switch (op) {
-    case 0: store_sim3(out + 8 * k, exp_sim3(a + 7 * k)); break;
-    case 1: store_sim3(out + 8 * k, retract_f64(a + 7 * k, load_sim3(b + 8 * k))); break;
-    case 2: store_sim3(out + 8 * k, compose(load_sim3(a + 8 * k), load_sim3(b + 8 * k))); break;
-    case 3: store_sim3(out + 8 * k, inverse(load_sim3(a + 8 * k))); break;
-    case 4: store_sim3(out + 8 * k, relative(load_sim3(a + 8 * k), load_sim3(b + 8 * k))); break;
-    case 5: act(load_sim3(a + 8 * k), b + 3 * k, out + 3 * k); break;
-    case 6: act(sim3_matrix(load_sim3(a + 8 * k)), b + 3 * k, out + 3 * k); break;
-    case 7: {
-      double M[7][7];
-      adjT_inv_matrix(a + 8 * k, M);
-      for (int r = 0; r < 7; r++)
-        for (int c = 0; c < 7; c++) out[49 * k + 7 * r + c] = (float)M[r][c];
-      break;
-    }
-    case 8: store_sim3(out + 8 * k, retract(a + 7 * k, load_sim3(b + 8 * k))); break;
-    default: break;
-  }
-}
+#include "gn/debug.h"
 
 }  // namespace
 

@@ -1,6 +1,7 @@
 """CPU check of csrc/m3s_gn.hip's layout: the files under csrc/gn/ are parts of
 that one translation unit. Each is included by m3s_gn.hip exactly once and
-includes nothing itself; an orphaned part would be dead code that looks alive."""
+includes nothing itself; an orphaned part would be dead code that looks alive.
+Each part opens by naming itself."""
 import os
 import re
 
@@ -15,3 +16,11 @@ def test_every_part_is_included_once():
     for p in parts:
         text = open(os.path.join(CSRC, "gn", p)).read()
         assert not re.search(r"^\s*#\s*include\b", text, re.M), p
+
+
+def test_every_part_opens_by_naming_itself():
+    parts = sorted(os.listdir(os.path.join(CSRC, "gn")))
+    assert parts
+    for p in parts:
+        first = open(os.path.join(CSRC, "gn", p), encoding="utf-8").readline()
+        assert first.startswith(f"// gn/{p} — part of the m3s_gn.hip translation unit"), p
