@@ -1,8 +1,7 @@
 // gn/args.h — part of the m3s_gn.hip translation unit (not a stand-alone header).
 // The small host helpers every host part uses: S() (the caller's stream),
 // launch_ok, make_params, check_args.
-// Host code only; relies on gn_layout (m3s_gn.hip above the include list) and
-// m3s_gn.h.
+// Host code only; relies on gn_layout (gn/layout.h) and m3s_gn.h.
 
 // ---------------------------------------------------------------- host --
 inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }

@@ -1,8 +1,8 @@
 // gn/border.h — part of the m3s_gn.hip translation unit (not a stand-alone header).
 // border_kernel: the dense tail's border updates over the chip, between the
 // two phases of sparse_llt_kernel<0>.
-// Relies on m3s_gn.hip above the include list: kFlagStop, and SparseDev,
-// border_task and kStageDoubles of the block-sparse LLT section.
+// Relies on kFlagStop (gn/layout.h) and on SparseDev, border_task and
+// kStageDoubles (gn/llt_blocks.h).
 
 // ------------------------------------------------------- border kernel --
 // Dense-tail border updates spread over the chip (global factors, between

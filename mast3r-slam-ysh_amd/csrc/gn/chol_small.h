@@ -2,8 +2,8 @@
 // Test build only (the whole part is inside #ifdef M3S_TEST_PATHS):
 // chol_small_kernel<NBC>, the register-resident dense Cholesky of one
 // workgroup, an A/B reference behind the dense knob.
-// Relies on m3s_gn.hip above the include list: kCholThreads, and finish_step
-// and fail_step of the section "assemble".
+// Relies on kCholThreads (gn/layout.h) and on finish_step and fail_step
+// (gn/assemble.h).
 
 #ifdef M3S_TEST_PATHS  // reached only through the dense knob: every graph it fits (m <= 31) has a sparse plan
 // ------------------------------------------------- small dense Cholesky --

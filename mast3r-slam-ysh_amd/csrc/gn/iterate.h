@@ -2,8 +2,8 @@
 // One GN iteration and the whole call: gn_linearize_impl, gn_solve_impl (the
 // first host mention of every solver kernel), set_lds_attributes_once, the
 // in-call timing (CallTiming, call_mark) and gn_full.
-// Relies on every kernel of m3s_gn.hip above the include list and on every
-// part before it (the kernel parts, gn/args.h and the three host parts).
+// Relies on every part before it: gn/layout.h, every kernel part, gn/args.h
+// and the three host parts.
 
 int gn_linearize_impl(const m3s_gn_args *a, const ResidualParams &P, int64_t eb, int64_t ee,
                       double *edge_sums, hipStream_t st, bool fuse_fin = false, int64_t *chunks_used = nullptr) {

@@ -2,8 +2,8 @@
 // The linearize launches of the host: the in-call timing event slots,
 // launch_lin, launch_linearize, dispatch_linearize (the first host mention of
 // the linearize kernel templates), vec_ok and read_K.
-// Relies on the linearize and gathering kernels (m3s_gn.hip, above the
-// include list), launch_ok (gn/args.h) and gn/knobs.h (gather_lds_path).
+// Relies on the linearize and gathering kernels (gn/linearize.h,
+// gn/gather.h), launch_ok (gn/args.h) and gn/knobs.h (gather_lds_path).
 
 // In-call timing (m3s_debug_call_timing): the drop-in call sets a start /
 // stop event pair for its next linearize launch, which then goes through

@@ -3,8 +3,8 @@
 // pinned staging, the plan cache, set_knob, build_plan_meta, build_eorder,
 // upload_plan, gn_prepare_impl (host prepare), finish_plan / host_finish and
 // gn_prepare_async (the prologue launch).
-// Relies on m3s_gn.hip above the include list (Layout / gn_layout,
-// kStageDoubles, kSplitUpdates), gn/prologue.h (the call prologue), gn/args.h
+// Relies on gn/layout.h (Layout / gn_layout), gn/llt_blocks.h
+// (kStageDoubles, kSplitUpdates), gn/prologue.h (the call prologue), gn/args.h
 // (S, launch_ok) and gn/knobs.h; declares set_lds_attributes_once, which
 // gn/iterate.h defines.
 

@@ -3,7 +3,7 @@
 // lower-bound helpers, gn_prologue_kernel (ranks the edge ids, writes the
 // linearize edge order, flags, info, dx) and its launch sizes (prologue_lds,
 // prologue_p2; host).
-// Relies on nothing but kFlagStop (m3s_gn.hip above the include list).
+// Relies on nothing but kFlagStop (gn/layout.h).
 
 // ------------------------------------------------------ call prologue --
 // The per-call setup of a GN call on the device, so the call's first

@@ -5,11 +5,11 @@
 // tail_pair_kernel, behind the test-only tail_pair knob). The part closes
 // with the introduction of tail_pair_kernel ("Round 4"); the kernel stands in
 // gn/tail_pair.h, behind the code it shares a launch with.
-// Relies on m3s_gn.hip above the include list: kTailMaxT and the flags,
-// sum_xor16_32 (linearize), the block-sparse LLT section (f64x4, ld_sc1 /
-// st_sc1, poll_b128, wave_lds_fence), the column-task section (kColSpins,
-// M3S_CSTAMP) and the f64 MFMA tail (TailArgs, tail_src / tail_entry,
-// tail_diag_mfma, tail_diag_warm, tail_tile, kTailNW).
+// Relies on gn/layout.h (kTailMaxT and the flags), sum_xor16_32
+// (gn/linearize.h), gn/llt_blocks.h (f64x4, ld_sc1 / st_sc1, poll_b128,
+// wave_lds_fence), gn/col_tasks.h (kColSpins, M3S_CSTAMP) and gn/tail_llt.h
+// (TailArgs, tail_src / tail_entry, tail_diag_mfma, tail_diag_warm,
+// tail_tile, kTailNW).
 
 // ----------------------------- dense tail over many workgroups (default) --
 // The same left-looking 16x16-tile factorisation as tail_llt_kernel, with

@@ -3,13 +3,12 @@
 // gcol_worker (the sparse columns' back-substitution, run by the launch's
 // extra workgroups while the tail factors), then tail_pair_kernel<RC> (two
 // tile columns per workgroup; introduced at the end of gn/tail_cyc.h).
-// Relies on m3s_gn.hip above the include list: kTailMaxT and the flags, the
-// wave sums of the linearize section (xred_index, xreduceN_dpp), the
-// block-sparse LLT section (f64x4, ld_sc1 / st_sc1, wave_lds_fence), the
-// column-task section (ColArgs, kColSpins, M3S_CSTAMP, set_fail,
-// wave_gticket), col_finish (dataflow), the f64 MFMA tail (TailArgs, the
-// diagonal tile, tail_tile, kTailNW); and on gn/tail_cyc.h (TailSync, the
-// granules, tail_backsub_wg).
+// Relies on gn/layout.h (kTailMaxT and the flags), the wave sums of
+// gn/linearize.h (xred_index, xreduceN_dpp), gn/llt_blocks.h (f64x4, ld_sc1 /
+// st_sc1, wave_lds_fence), gn/col_tasks.h (ColArgs, kColSpins, M3S_CSTAMP,
+// set_fail, wave_gticket), col_finish (gn/dataflow.h), gn/tail_llt.h
+// (TailArgs, the diagonal tile, tail_tile, kTailNW) and gn/tail_cyc.h
+// (TailSync, the granules, tail_backsub_wg).
 
 // ------------------------ sparse back-substitution beside the dense tail --
 // Round 5: the sparse back-substitution off the critical path. The sparse

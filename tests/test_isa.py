@@ -1,5 +1,5 @@
 """CPU check of the built library's gfx950 code (no GPU): the pipelined
-gathering kernel's counted wait (linearize_gather_kernel, m3s_gn.hip) is only
+gathering kernel's counted wait (linearize_gather_kernel, gn/gather.h) is only
 correct if at least NPL vector-memory operations follow the 8 LDS-DMA refill
 loads on every path back to the loop top's `s_waitcnt vmcnt(NPL)` (vmcnt counts
 in issue order; the inline-asm LDS reads of the slot are invisible to the
@@ -143,7 +143,7 @@ def kernel_base(text, mode):
 # the loop (a plain read-only load in a loop that stores nothing may be), the
 # wait can only time out: round 4 saw exactly that in the tracker once its
 # s_sleep was removed (profiles/r04/trk_ab_sleep0_INVALID.txt). The loads are
-# now poll_b128 (m3s_gn.hip: a compiler memory barrier in front of each) or
+# now poll_b128 (gn/llt_blocks.h: a compiler memory barrier in front of each) or
 # agent-scope atomics. These tests find the loops in the machine code (natural
 # loops of the control-flow graph) and check that each one reads memory.
 

@@ -1,5 +1,5 @@
 // Micro-benchmark (gfx950): the dense tail's 16x16 diagonal factor on DPP row
-// broadcasts (m3s_gn.hip tail_diag_full, restated) on one wave, hot calls,
+// broadcasts (gn/tail_llt.h tail_diag_full, restated) on one wave, hot calls,
 // shader clock; plus the latency of its building blocks (dependent f64 FMA,
 // v_mov_b64_dpp row_newbcast -> FMA, rsqrt_nr) with no loop overhead.
 //   hipcc --offload-arch=gfx950 -O3 tools/ubench_diag16.hip -o variants/ubench_diag16

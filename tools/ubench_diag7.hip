@@ -1,5 +1,5 @@
 // Micro-benchmark of the 7x7 DIAG factor of sparse_llt_kernel (gfx950): the
-// same algorithm as m3s_gn.hip's diag_factor<false, RL=true> (restated here,
+// same algorithm as gn/llt_blocks.h's diag_factor<false, RL=true> (restated here,
 // hot code, one wave alone on its SIMD), with shader-clock stamps after the
 // entry -> row relayout, after the pivot loop and after the stores, and
 // variants of the pivot loop.

@@ -1,7 +1,7 @@
 // Micro-benchmarks, part 2 (gfx950): straight-line code run cold vs hot
 // (instruction-cache misses in one-shot chain code), dependent f64 FMA and
 // v_rsq_f64 latencies, and the dense tail's 16x16 diagonal factor (the same
-// algorithm as m3s_gn.hip's tail_diag_mfma_t, restated here) per call, first
+// algorithm as gn/tail_llt.h's tail_diag_mfma_t, restated here) per call, first
 // call vs later calls.
 //   hipcc --offload-arch=gfx950 -O3 tools/ubench_icache.hip -o variants/ubench_icache
 #include <hip/hip_runtime.h>
