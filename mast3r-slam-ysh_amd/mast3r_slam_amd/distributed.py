@@ -21,8 +21,6 @@ implementation to exercise the slicing and the collective on gloo.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.distributed as dist
 
@@ -109,43 +107,28 @@ class HipOps:
         self.dx = torch.zeros(max(N - 1, 0), 7, dtype=torch.float32, device=dev)
         self.info = torch.zeros(8, dtype=torch.int32, device=dev)
         self.ws = be._workspace(be._lib.m3s_gn_workspace_size(N, HW, int(E)), dev)
-        a = be.GnArgs()
-        P = be._p
-        a.Twc, a.Xs, a.Cs, a.ii, a.jj = P(Twc), P(Xs), P(Cs), P(ii), P(jj)
-        # edge-slice base pointers: the C side addresses edge data relative to
-        # edge_begin (include/m3s_gn.h, stepwise API)
-        a.idx_ii2jj, a.valid_match, a.Q, a.K = P(idx_loc), P(valid_loc), P(Q_loc), P(K)
-        a.idx_i32 = 1 if idx_loc.dtype == torch.int32 else 0
-        a.N, a.HW, a.E, a.mode = N, HW, int(E), mode
-        a.sigma_a, a.sigma_b, a.C_thresh, a.Q_thresh = sigma_a, sigma_b, C_thresh, Q_thresh
-        a.height, a.width, a.pixel_border, a.z_eps = height, width, pixel_border, z_eps
-        a.max_iter, a.delta_thresh = 0, 0.0
-        a.dx_out, a.info = P(self.dx), P(self.info)
-        a.workspace, a.workspace_bytes = P(self.ws), self.ws.numel()
-        self.args = a
-        self.keep = dict(Twc=Twc, Xs=Xs, Cs=Cs, ii=ii, jj=jj, idx=idx_loc, valid=valid_loc,
-                         Q=Q_loc, K=K)
-        self.stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        # idx / valid / Q are edge-slice base pointers: the C side addresses edge
+        # data relative to edge_begin (include/m3s_gn.h, stepwise API), so E is
+        # given here, not read from them; the stepwise calls take no max_iter
+        self.args, self.keep = be.fill_gn_args(
+            mode, Twc, Xs, Cs, ii, jj, idx_loc, valid_loc, Q_loc, K, N, HW, E, sigma_a=sigma_a, sigma_b=sigma_b,
+            C_thresh=C_thresh, Q_thresh=Q_thresh, height=height, width=width, pixel_border=pixel_border,
+            z_eps=z_eps, max_iter=0, delta_thresh=0.0, dx=self.dx, info=self.info, workspace=self.ws)
 
     def prepare(self, delta_thresh: float):
         self.args.delta_thresh = float(delta_thresh)
-        self.be._raise(self.be._lib.m3s_gn_prepare(ctypes.byref(self.args), self.stream),
-                       "m3s_gn_prepare")
+        self.be.gn_prepare(self.args, self.keep)
 
     def linearize(self, eb: int, ee: int, es_loc):
-        ptr = self.be._p(es_loc) if es_loc is not None else None
-        self.be._raise(self.be._lib.m3s_gn_linearize(ctypes.byref(self.args), eb, ee, ptr,
-                                                     self.stream), "m3s_gn_linearize")
+        self.be.gn_linearize(self.args, self.keep, eb, ee, es_loc)
 
     def solve(self, es):
-        self.be._raise(self.be._lib.m3s_gn_solve(ctypes.byref(self.args), self.be._p(es),
-                                                 self.stream), "m3s_gn_solve")
+        self.be.gn_solve(self.args, self.keep, es)
 
     def close(self):
         """Drop the library's host state of this workspace (m3s_gn_release)."""
         if self.args is not None:
-            self.be._raise(self.be._lib.m3s_gn_release(ctypes.byref(self.args), self.stream),
-                           "m3s_gn_release")
+            self.be.gn_release(self.args, self.keep)
             self.args = None
 
 

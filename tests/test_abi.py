@@ -2,21 +2,18 @@
 
 * libm3s_gn.so loads and exports every symbol include/m3s_gn.h declares;
 * the ctypes mirrors of m3s_gn_args / m3s_track_args have exactly the C
-  layout (a gcc-compiled probe prints sizeof/offsetof from the header);
+  layout (tests/abi_probe.py: sizeof and every offsetof, from the header);
 * workspace sizing is monotone and covers the documented sections;
 * the drop-in module exposes the reference's five entry points (gn.cpp:116-122)
   and rejects CPU tensors / non-contiguous inputs before touching the device.
 """
 import os
-import re
-import subprocess
 
+import abi_probe
 import pytest
 import torch
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-HEADER = os.path.join(ROOT, "include", "m3s_gn.h")
-HEADERS = [HEADER, os.path.join(ROOT, "include", "m3s_match.h"), os.path.join(ROOT, "include", "m3s_fuse.h")]
+HEADERS = ["m3s_gn.h", "m3s_match.h", "m3s_fuse.h"]
 
 
 @pytest.fixture(scope="module")
@@ -27,8 +24,7 @@ def be():
 
 
 def test_library_exports_every_header_symbol(be):
-    src = "".join(open(h).read() for h in HEADERS)
-    declared = set(re.findall(r"\b(m3s_[a-z0-9_]+)\s*\(", src))
+    declared = set().union(*(abi_probe.declared_symbols(h) for h in HEADERS))
     assert declared == set(be.EXPORTS)
     for sym in declared:
         assert hasattr(be._lib, sym), sym
@@ -48,56 +44,11 @@ def test_reference_entry_points_present(be):
                           torch.zeros(1, 16, 2, dtype=torch.int64), 3, 5)
 
 
-PROBE = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "m3s_gn.h"
-#include "m3s_match.h"
-#include "m3s_fuse.h"
-#define F(T, m) printf(#T "." #m " %zu\n", offsetof(T, m))
-int main(void) {
-  printf("m3s_gn_args.size %zu\n", sizeof(m3s_gn_args));
-  F(m3s_gn_args, Twc); F(m3s_gn_args, K); F(m3s_gn_args, N); F(m3s_gn_args, mode);
-  F(m3s_gn_args, sigma_a); F(m3s_gn_args, z_eps); F(m3s_gn_args, max_iter);
-  F(m3s_gn_args, delta_thresh); F(m3s_gn_args, dx_out); F(m3s_gn_args, info);
-  F(m3s_gn_args, workspace); F(m3s_gn_args, workspace_bytes);
-  printf("m3s_track_args.size %zu\n", sizeof(m3s_track_args));
-  F(m3s_track_args, K); F(m3s_track_args, HW); F(m3s_track_args, height); F(m3s_track_args, z_eps);
-  F(m3s_track_args, huber_k); F(m3s_track_args, max_iters); F(m3s_track_args, sync_every);
-  F(m3s_track_args, T_WCf_out); F(m3s_track_args, workspace_bytes);
-  printf("m3s_iter_proj_args.size %zu\n", sizeof(m3s_iter_proj_args));
-  F(m3s_iter_proj_args, B); F(m3s_iter_proj_args, N); F(m3s_iter_proj_args, max_iter);
-  F(m3s_iter_proj_args, lambda_init); F(m3s_iter_proj_args, cost_thresh);
-  F(m3s_iter_proj_args, p_new); F(m3s_iter_proj_args, converged);
-  printf("m3s_refine_args.size %zu\n", sizeof(m3s_refine_args));
-  F(m3s_refine_args, p1); F(m3s_refine_args, F); F(m3s_refine_args, dtype);
-  F(m3s_refine_args, radius); F(m3s_refine_args, dilation_max); F(m3s_refine_args, p1_new);
-  printf("m3s_fuse_args.size %zu\n", sizeof(m3s_fuse_args));
-  F(m3s_fuse_args, T); F(m3s_fuse_args, HW); F(m3s_fuse_args, mode);
-  printf("m3s_prep_rays_args.size %zu\n", sizeof(m3s_prep_rays_args));
-  F(m3s_prep_rays_args, B); F(m3s_prep_rays_args, W); F(m3s_prep_rays_args, pts_norm);
-  return 0;
-}
-"""
-
-
-def test_ctypes_struct_layout_matches_header(be, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-I", os.path.dirname(HEADER), str(c), "-o", str(exe)])
-    out = subprocess.check_output([str(exe)]).decode().split("\n")
-    got = dict(l.split() for l in out if l.strip())
-    mirror = {"m3s_gn_args": be.GnArgs, "m3s_track_args": be.TrackArgs,
-              "m3s_iter_proj_args": be.IterProjArgs, "m3s_refine_args": be.RefineArgs,
-              "m3s_fuse_args": be.FuseArgs, "m3s_prep_rays_args": be.PrepRaysArgs}
-    for key, val in got.items():
-        t, m = key.split(".")
-        cls = mirror[t]
-        if m == "size":
-            assert int(val) == __import__("ctypes").sizeof(cls), key
-        else:
-            assert int(val) == getattr(cls, m).offset, key
+def test_ctypes_struct_layout_matches_header(be):
+    # every field of every mirror, by its _fields_
+    abi_probe.probe(HEADERS, {"m3s_gn_args": be.GnArgs, "m3s_track_args": be.TrackArgs,
+                              "m3s_iter_proj_args": be.IterProjArgs, "m3s_refine_args": be.RefineArgs,
+                              "m3s_fuse_args": be.FuseArgs, "m3s_prep_rays_args": be.PrepRaysArgs})
 
 
 def test_workspace_size_monotone(be):

@@ -8,30 +8,13 @@ modules, whose forward then falls back, bitwise, wherever the kernel does not
 apply (as everywhere on the CPU)."""
 import ctypes
 import math
-import os
-import re
-import subprocess
 
+import abi_probe
 import pytest
 import torch
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-INCLUDE = os.path.join(ROOT, "include")
-
 FIELDS = ("q", "k", "v", "out", "qpos", "kpos", "B", "Nq", "Nk", "H", "D",
           "q_sb", "q_sn", "k_sb", "k_sn", "v_sb", "v_sn", "o_sb", "o_sn", "base", "f0", "scale", "dtype")
-
-PROBE = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "m3s_attn.h"
-#define F(m) printf(#m " %zu\n", offsetof(m3s_attn_args, m))
-int main(void) {
-  printf("f32 %d\nsize %zu\n", M3S_ROPE_F32, sizeof(m3s_attn_args));
-""" + "\n".join(f"  F({m});" for m in FIELDS) + r"""
-  return 0;
-}
-"""
 
 
 @pytest.fixture(scope="module")
@@ -41,24 +24,14 @@ def be():
     return be
 
 
-def test_ctypes_mirror_matches_header(be, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-I", INCLUDE, str(c), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    assert int(got.pop("f32")) == be.ROPE_F32
-    assert int(got.pop("size")) == ctypes.sizeof(be.AttnArgs)
+def test_ctypes_mirror_matches_header(be):
     assert tuple(n for n, _ in be.AttnArgs._fields_) == FIELDS
-    assert set(got) == set(FIELDS)
-    for m in FIELDS:
-        assert int(got[m]) == getattr(be.AttnArgs, m).offset, m
+    got = abi_probe.probe(["m3s_attn.h"], {"m3s_attn_args": be.AttnArgs}, ["M3S_ROPE_F32"])
+    assert got["M3S_ROPE_F32"] == be.ROPE_F32
 
 
 def test_header_symbols_are_attn_exports(be):
-    with open(os.path.join(INCLUDE, "m3s_attn.h")) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    declared = set(re.findall(r"\b(m3s_\w+)\s*\(", text))
+    declared = abi_probe.declared_symbols("m3s_attn.h")
     assert declared == set(be.ATTN_EXPORTS) == {"m3s_attn_rope"}
     for sym in be.ATTN_EXPORTS:
         assert hasattr(be._lib, sym), sym

@@ -8,30 +8,13 @@ right heads of a stand-in model."""
 import ctypes
 import functools
 import math
-import os
-import re
-import subprocess
 
+import abi_probe
 import pytest
 import torch
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-INCLUDE = os.path.join(ROOT, "include")
-
 FIELDS = ("pts", "feat", "X", "C", "D", "Q", "B", "H", "W", "P", "F", "ds", "sbX", "sbC", "sbD", "sbQ",
           "conf_vmin", "conf_vmax", "dconf_vmin", "dconf_vmax", "desc_dtype", "flags")
-
-PROBE = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "m3s_head.h"
-#define F(m) printf(#m " %zu\n", offsetof(m3s_head_args, m))
-int main(void) {
-  printf("f32 %d\nf16 %d\ngeneric %d\nsize %zu\n", M3S_HEAD_F32, M3S_HEAD_F16, M3S_HEAD_GENERIC, sizeof(m3s_head_args));
-""" + "\n".join(f"  F({m});" for m in FIELDS) + r"""
-  return 0;
-}
-"""
 
 
 @pytest.fixture(scope="module")
@@ -41,24 +24,15 @@ def be():
     return be
 
 
-def test_ctypes_mirror_matches_header(be, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-I", INCLUDE, str(c), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    assert (int(got.pop("f32")), int(got.pop("f16")), int(got.pop("generic"))) == (be.HEAD_F32, be.HEAD_F16, be.HEAD_GENERIC)
-    assert int(got.pop("size")) == ctypes.sizeof(be.HeadArgs)
+def test_ctypes_mirror_matches_header(be):
     assert tuple(n for n, _ in be.HeadArgs._fields_) == FIELDS
-    assert set(got) == set(FIELDS)
-    for m in FIELDS:
-        assert int(got[m]) == getattr(be.HeadArgs, m).offset, m
+    got = abi_probe.probe(["m3s_head.h"], {"m3s_head_args": be.HeadArgs},
+                          ["M3S_HEAD_F32", "M3S_HEAD_F16", "M3S_HEAD_GENERIC"])
+    assert (got["M3S_HEAD_F32"], got["M3S_HEAD_F16"], got["M3S_HEAD_GENERIC"]) == (be.HEAD_F32, be.HEAD_F16, be.HEAD_GENERIC)
 
 
 def test_header_symbols_are_head_exports(be):
-    with open(os.path.join(INCLUDE, "m3s_head.h")) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    declared = set(re.findall(r"\b(m3s_\w+)\s*\(", text))
+    declared = abi_probe.declared_symbols("m3s_head.h")
     assert declared == set(be.HEAD_EXPORTS) == {"m3s_head_postprocess"}
     for sym in be.HEAD_EXPORTS:
         assert hasattr(be._lib, sym), sym

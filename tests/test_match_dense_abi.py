@@ -3,31 +3,14 @@ tests/test_abi.py: the ctypes mirror of m3s_match_dense_args has exactly the C
 layout (a gcc-compiled probe prints sizeof / offsetof from the header), the
 workspace size grows with B, H and W, and the wrapper turns away CPU tensors
 before it touches the device."""
-import ctypes
-import os
-import subprocess
 
+import abi_probe
 import pytest
 import torch
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-INCLUDE = os.path.join(ROOT, "include")
 
 FIELDS = ("X11", "X21", "D11", "D21", "Q11", "Q21", "idx_init", "B", "H", "W", "F", "dtype", "max_iter",
           "lambda_init", "cost_thresh", "dist_thresh", "radius", "dilation_max", "Q_conf", "idx", "valid", "Q",
           "idx_stride", "valid_stride", "Q_stride", "n_valid", "workspace", "workspace_bytes")
-
-PROBE = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "m3s_match.h"
-#define F(m) printf(#m " %zu\n", offsetof(m3s_match_dense_args, m))
-int main(void) {
-  printf("size %zu\n", sizeof(m3s_match_dense_args));
-  """ + " ".join(f"F({m});" for m in FIELDS) + r"""
-  return 0;
-}
-"""
 
 
 @pytest.fixture(scope="module")
@@ -37,17 +20,9 @@ def be():
     return be
 
 
-def test_ctypes_struct_layout_matches_header(be, tmp_path):
+def test_ctypes_struct_layout_matches_header(be):
     assert tuple(n for n, _ in be.MatchDenseArgs._fields_) == FIELDS
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-I", INCLUDE, str(c), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    assert int(got.pop("size")) == ctypes.sizeof(be.MatchDenseArgs)
-    assert set(got) == set(FIELDS)
-    for m, off in got.items():
-        assert int(off) == getattr(be.MatchDenseArgs, m).offset, m
+    abi_probe.probe(["m3s_match.h"], {"m3s_match_dense_args": be.MatchDenseArgs})
 
 
 def test_workspace_size_monotone(be):

@@ -6,29 +6,13 @@ be.RETRIEVAL_EXPORTS and in the library, the workspace size is monotone, every
 documented M3S_EINVAL condition is refused with a null stream and no device,
 and the Python layers refuse CPU tensors and unknown quantizers."""
 import ctypes
-import os
-import subprocess
 
+import abi_probe
 import pytest
 import torch
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-INCLUDE = os.path.join(ROOT, "include")
-
 FIELDS = ("des", "centroids", "norms", "n", "Kc", "D", "ma", "assign", "dist", "workspace", "workspace_bytes")
 NEW_SYMBOLS = ("m3s_asmk_quantize_workspace_size", "m3s_asmk_centroid_norms", "m3s_asmk_quantize")
-
-PROBE = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "m3s_retrieval.h"
-#define F(m) printf(#m " %zu\n", offsetof(m3s_asmk_quantize_args, m))
-int main(void) {
-  printf("max_ma %d\nsize %zu\n", M3S_ASMK_QUANTIZE_MAX_MA, sizeof(m3s_asmk_quantize_args));
-""" + "\n".join(f"  F({m});" for m in FIELDS) + r"""
-  return 0;
-}
-"""
 
 
 @pytest.fixture(scope="module")
@@ -38,18 +22,11 @@ def be():
     return be
 
 
-def test_ctypes_mirror_matches_header(be, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-I", INCLUDE, str(c), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    assert int(got.pop("max_ma")) == be.ASMK_QUANTIZE_MAX_MA == 8
-    assert int(got.pop("size")) == ctypes.sizeof(be.AsmkQuantizeArgs)
+def test_ctypes_mirror_matches_header(be):
     assert tuple(n for n, _ in be.AsmkQuantizeArgs._fields_) == FIELDS
-    assert set(got) == set(FIELDS)
-    for m in FIELDS:
-        assert int(got[m]) == getattr(be.AsmkQuantizeArgs, m).offset, m
+    got = abi_probe.probe(["m3s_retrieval.h"], {"m3s_asmk_quantize_args": be.AsmkQuantizeArgs},
+                          ["M3S_ASMK_QUANTIZE_MAX_MA"])
+    assert got["M3S_ASMK_QUANTIZE_MAX_MA"] == be.ASMK_QUANTIZE_MAX_MA == 8
 
 
 def test_new_symbols_listed_and_exported(be):

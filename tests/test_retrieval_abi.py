@@ -6,16 +6,10 @@ library exports them, the size functions are monotone, unsupported settings
 and CPU tensors are refused before the device is touched, and backend_edges
 restates main.py:103-125."""
 import ctypes
-import os
-import re
-import subprocess
 
+import abi_probe
 import pytest
 import torch
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-INCLUDE = os.path.join(ROOT, "include")
-HEADER = os.path.join(INCLUDE, "m3s_retrieval.h")
 
 STRUCTS = {
     "m3s_asmk_out": ("AsmkOut", ("count", "n_images", "info", "n_query_words", "idx", "score")),
@@ -27,21 +21,6 @@ STRUCTS = {
                                                 "min_thresh")),
 }
 
-PROBE = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "m3s_retrieval.h"
-#define F(T, m) printf(#T "." #m " %zu\n", offsetof(T, m))
-int main(void) {
-  printf("consts.max_pairs %d\nconsts.max_k %d\nconsts.bad_word %d\nconsts.full %d\n", M3S_ASMK_MAX_PAIRS,
-         M3S_ASMK_MAX_K, M3S_ASMK_INFO_BAD_WORD, M3S_ASMK_INFO_FULL);
-  printf("consts.store_sections %d\nconsts.ws_sections %d\n", M3S_ASMK_STORE_SECTIONS, M3S_ASMK_WS_SECTIONS);
-""" + "\n".join(f'  printf("{t}.size %zu\\n", sizeof({t})); ' + " ".join(f"F({t}, {m});" for m in fields)
-                for t, (_, fields) in STRUCTS.items()) + r"""
-  return 0;
-}
-"""
-
 
 @pytest.fixture(scope="module")
 def be():
@@ -50,33 +29,22 @@ def be():
     return be
 
 
-def test_ctypes_struct_layout_matches_header(be, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-I", INCLUDE, str(c), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    assert int(got.pop("consts.max_pairs")) == be.ASMK_MAX_PAIRS == 4096
-    assert int(got.pop("consts.max_k")) == be.ASMK_MAX_K
-    assert int(got.pop("consts.bad_word")) == be.ASMK_INFO_BAD_WORD
-    assert int(got.pop("consts.full")) == be.ASMK_INFO_FULL
-    assert int(got.pop("consts.store_sections")) == len(be.ASMK_STORE_SECTIONS)
-    assert int(got.pop("consts.ws_sections")) == len(be.ASMK_WS_SECTIONS)
-    seen = 0
-    for key, val in got.items():
-        t, m = key.split(".")
-        cls = getattr(be, STRUCTS[t][0])
-        assert tuple(n for n, _ in cls._fields_) == STRUCTS[t][1]
-        if m == "size":
-            assert int(val) == ctypes.sizeof(cls), key
-        else:
-            assert int(val) == getattr(cls, m).offset, key
-        seen += 1
-    assert seen == sum(1 + len(f) for _, f in STRUCTS.values())
+def test_ctypes_struct_layout_matches_header(be):
+    for name, fields in STRUCTS.values():
+        assert tuple(n for n, _ in getattr(be, name)._fields_) == fields
+    got = abi_probe.probe(["m3s_retrieval.h"], {t: getattr(be, name) for t, (name, _) in STRUCTS.items()},
+                          ["M3S_ASMK_MAX_PAIRS", "M3S_ASMK_MAX_K", "M3S_ASMK_INFO_BAD_WORD", "M3S_ASMK_INFO_FULL",
+                           "M3S_ASMK_STORE_SECTIONS", "M3S_ASMK_WS_SECTIONS"])
+    assert got["M3S_ASMK_MAX_PAIRS"] == be.ASMK_MAX_PAIRS == 4096
+    assert got["M3S_ASMK_MAX_K"] == be.ASMK_MAX_K
+    assert got["M3S_ASMK_INFO_BAD_WORD"] == be.ASMK_INFO_BAD_WORD
+    assert got["M3S_ASMK_INFO_FULL"] == be.ASMK_INFO_FULL
+    assert got["M3S_ASMK_STORE_SECTIONS"] == len(be.ASMK_STORE_SECTIONS)
+    assert got["M3S_ASMK_WS_SECTIONS"] == len(be.ASMK_WS_SECTIONS)
 
 
 def test_library_exports_every_header_symbol(be):
-    declared = set(re.findall(r"\b(m3s_[a-z0-9_]+)\s*\(", open(HEADER).read()))
+    declared = abi_probe.declared_symbols("m3s_retrieval.h")
     assert declared == set(be.RETRIEVAL_EXPORTS)
     assert not declared & set(be.EXPORTS)
     for sym in declared:

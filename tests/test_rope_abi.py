@@ -6,29 +6,12 @@ M3S_EINVAL condition is refused with a null stream and no device, the Python
 wrapper refuses what it cannot take, and rope.install swaps the right modules."""
 import ctypes
 import math
-import os
-import re
-import subprocess
 
+import abi_probe
 import pytest
 import torch
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-INCLUDE = os.path.join(ROOT, "include")
-
 FIELDS = ("tokens", "pos", "B", "N", "H", "D", "stride_b", "stride_n", "base", "f0", "dtype")
-
-PROBE = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "m3s_rope.h"
-#define F(m) printf(#m " %zu\n", offsetof(m3s_rope_args, m))
-int main(void) {
-  printf("f32 %d\nf16 %d\nbf16 %d\nsize %zu\n", M3S_ROPE_F32, M3S_ROPE_F16, M3S_ROPE_BF16, sizeof(m3s_rope_args));
-""" + "\n".join(f"  F({m});" for m in FIELDS) + r"""
-  return 0;
-}
-"""
 
 
 @pytest.fixture(scope="module")
@@ -38,24 +21,14 @@ def be():
     return be
 
 
-def test_ctypes_mirror_matches_header(be, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-I", INCLUDE, str(c), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    assert (int(got.pop("f32")), int(got.pop("f16")), int(got.pop("bf16"))) == (be.ROPE_F32, be.ROPE_F16, be.ROPE_BF16)
-    assert int(got.pop("size")) == ctypes.sizeof(be.RopeArgs)
+def test_ctypes_mirror_matches_header(be):
     assert tuple(n for n, _ in be.RopeArgs._fields_) == FIELDS
-    assert set(got) == set(FIELDS)
-    for m in FIELDS:
-        assert int(got[m]) == getattr(be.RopeArgs, m).offset, m
+    got = abi_probe.probe(["m3s_rope.h"], {"m3s_rope_args": be.RopeArgs}, ["M3S_ROPE_F32", "M3S_ROPE_F16", "M3S_ROPE_BF16"])
+    assert (got["M3S_ROPE_F32"], got["M3S_ROPE_F16"], got["M3S_ROPE_BF16"]) == (be.ROPE_F32, be.ROPE_F16, be.ROPE_BF16)
 
 
 def test_header_symbols_are_rope_exports(be):
-    with open(os.path.join(INCLUDE, "m3s_rope.h")) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    declared = set(re.findall(r"\b(m3s_\w+)\s*\(", text))
+    declared = abi_probe.declared_symbols("m3s_rope.h")
     assert declared == set(be.ROPE_EXPORTS) == {"m3s_rope_2d"}
     for sym in be.ROPE_EXPORTS:
         assert hasattr(be._lib, sym), sym

@@ -6,31 +6,15 @@ its own sections, argument errors come back as M3S_EINVAL before anything is
 launched, and the wrapper turns away CPU tensors before it touches the device
 (wrong dtypes and shapes on device tensors: tests/test_gpu_track_frame.py)."""
 import ctypes
-import os
-import subprocess
 
+import abi_probe
 import pytest
 import torch
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-INCLUDE = os.path.join(ROOT, "include")
 
 FIELDS = ("Xf_canon", "Cf_sum", "Xk_canon", "Ck_sum", "idx_f2k", "valid_match", "Qk", "T_WCf", "T_WCk", "K",
           "HW", "Nf", "Nk", "height", "width", "C_conf", "Q_conf", "pixel_border", "z_eps", "sigma_a", "sigma_b",
           "huber_k", "max_iters", "rel_error", "delta_norm", "sync_every", "T_WCf_out", "T_CkCf_out", "info",
           "stats", "Xf_out", "Xk_out", "valid_opt_out", "workspace", "workspace_bytes")
-
-PROBE = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "m3s_gn.h"
-#define F(m) printf(#m " %zu\n", offsetof(m3s_track_frame_args, m))
-int main(void) {
-  printf("size %zu\n", sizeof(m3s_track_frame_args));
-  """ + " ".join(f"F({m});" for m in FIELDS) + r"""
-  return 0;
-}
-"""
 
 
 @pytest.fixture(scope="module")
@@ -40,17 +24,9 @@ def be():
     return be
 
 
-def test_ctypes_struct_layout_matches_header(be, tmp_path):
+def test_ctypes_struct_layout_matches_header(be):
     assert tuple(n for n, _ in be.TrackFrameArgs._fields_) == FIELDS
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-I", INCLUDE, str(c), "-o", str(exe)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().split("\n") if l.strip())
-    assert int(got.pop("size")) == ctypes.sizeof(be.TrackFrameArgs)
-    assert set(got) == set(FIELDS)
-    for m, off in got.items():
-        assert int(off) == getattr(be.TrackFrameArgs, m).offset, m
+    abi_probe.probe(["m3s_gn.h"], {"m3s_track_frame_args": be.TrackFrameArgs})
 
 
 def test_symbols_exported(be):
