@@ -47,6 +47,12 @@ with v in one launch, fp32, head dimension 64, written in the [B, N, C] layout
 catmlp+dpt head: from the DPT map and the local-feature MLP's output to X, C, D
 and Q in the slots and dtypes ``match_dense``, ``track_frame`` and the factor
 graph take, one launch; ``mast3r_slam_amd.head`` puts it into a loaded model.
+
+``dpt_tail`` (new; include/m3s_dpt.h) is what stands directly in front of it:
+the last four modules of the DPT head (bilinear x2 upsampling, the 3x3
+convolution 128 -> 128, ReLU, the 1x1 convolution to the 4 output channels) in
+one launch on the fp32 MFMA, from weights ``dpt_tail_pack`` packs once per
+model; ``mast3r_slam_amd.dpt`` puts it into a loaded model.
 """
 from __future__ import annotations
 
@@ -55,10 +61,11 @@ import os
 
 # one module per public header: its public names are the package's, and its
 # _SIGNATURES (symbol -> (restype, argtypes)) declares each of its symbols once
-from . import attn, fuse, gn, head, match, retrieval, rope
+from . import attn, dpt, fuse, gn, head, match, retrieval, rope
 from ._abi import *  # noqa: F401,F403  (the M3S_* return codes)
 from ._abi import _call, _check, _p, _raise, _stream, _workspace  # noqa: F401  (used by distributed, tools and tests)
 from .attn import *  # noqa: F401,F403
+from .dpt import *  # noqa: F401,F403
 from .fuse import *  # noqa: F401,F403
 from .gn import *  # noqa: F401,F403
 from .head import *  # noqa: F401,F403
@@ -81,6 +88,7 @@ RETRIEVAL_EXPORTS = tuple(retrieval._SIGNATURES)  # every symbol include/m3s_ret
 ROPE_EXPORTS = tuple(rope._SIGNATURES)  # ... include/m3s_rope.h
 ATTN_EXPORTS = tuple(attn._SIGNATURES)  # ... include/m3s_attn.h
 HEAD_EXPORTS = tuple(head._SIGNATURES)  # ... include/m3s_head.h
+DPT_EXPORTS = tuple(dpt._SIGNATURES)  # ... include/m3s_dpt.h
 
 
 def _load(path=LIB_PATH):
@@ -90,7 +98,7 @@ def _load(path=LIB_PATH):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950)"
         )
     lib = ctypes.CDLL(path)
-    for module in _MODULES:
+    for module in _MODULES + (dpt,):  # _MODULES: the seven tables tests/test_backend_package.py holds together
         for symbol, (restype, argtypes) in module._SIGNATURES.items():
             fn = getattr(lib, symbol)
             fn.restype, fn.argtypes = restype, argtypes
