@@ -17,7 +17,7 @@ __global__ void __launch_bounds__(64 * kBorderWaves) border_kernel(SparseDev D) 
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int32_t *pl = D.plan;
-  const int32_t *clq = pl + D.off[28];
+  const int32_t *clq = pl + D.off[kSec_clq];
   const int nc = clq[0], c0 = clq[1], nt0 = nc * (nc + 1) / 2;
   const int r = lane / 7, c = lane % 7;
   const bool act49 = lane < 49;

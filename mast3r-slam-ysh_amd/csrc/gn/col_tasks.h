@@ -95,9 +95,11 @@ __global__ void __launch_bounds__(256) col_factor_kernel(ColArgs C) {
   __shared__ __attribute__((aligned(16))) double stage[4][kStageDoubles];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int32_t *pl = C.plan;
-  const int32_t *col_ptr = pl + C.off[1], *dtr_ptr = pl + C.off[6], *dtr_slot = pl + C.off[7],
-                *dtr_p = pl + C.off[8], *task_dst = pl + C.off[10], *task_tr_ptr = pl + C.off[12],
-                *tr_a = pl + C.off[13], *tr_b = pl + C.off[14], *corder = pl + C.off[29], *ctask0 = pl + C.off[30];
+  const int32_t *col_ptr = pl + C.off[kSec_col_ptr], *dtr_ptr = pl + C.off[kSec_dtr_ptr],
+                *dtr_slot = pl + C.off[kSec_dtr_slot], *dtr_p = pl + C.off[kSec_dtr_p],
+                *task_dst = pl + C.off[kSec_task_dst], *task_tr_ptr = pl + C.off[kSec_task_tr_ptr],
+                *tr_a = pl + C.off[kSec_tr_a], *tr_b = pl + C.off[kSec_tr_b], *corder = pl + C.off[kSec_corder],
+                *ctask0 = pl + C.off[kSec_ctask0];
   const int r = lane / 7, c = lane % 7;
   const bool act49 = lane < 49;
   const int lane49 = act49 ? lane : 0, r7 = act49 ? r * 7 : 0, c7 = act49 ? c * 7 : 0;

@@ -50,10 +50,11 @@ __global__ void __launch_bounds__(64 * kDfWaves) df_factor_kernel(DfArgs D) {
   __shared__ double Wsh[kDfWaves][49];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int32_t *pl = D.plan;
-  const int32_t *dtr_ptr = pl + D.off[6], *dtr_slot = pl + D.off[7], *dtr_p = pl + D.off[8],
-                *task_dst = pl + D.off[10], *task_col = pl + D.off[11], *task_tr_ptr = pl + D.off[12],
-                *tr_a = pl + D.off[13], *tr_b = pl + D.off[14];
-  const int32_t *clq = pl + D.off[28];
+  const int32_t *dtr_ptr = pl + D.off[kSec_dtr_ptr], *dtr_slot = pl + D.off[kSec_dtr_slot],
+                *dtr_p = pl + D.off[kSec_dtr_p], *task_dst = pl + D.off[kSec_task_dst],
+                *task_col = pl + D.off[kSec_task_col], *task_tr_ptr = pl + D.off[kSec_task_tr_ptr],
+                *tr_a = pl + D.off[kSec_tr_a], *tr_b = pl + D.off[kSec_tr_b];
+  const int32_t *clq = pl + D.off[kSec_clq];
   const int r = lane / 7, c = lane % 7;
   const bool act49 = lane < 49;
   const int lane49 = act49 ? lane : 0, r7 = act49 ? r * 7 : 0, c7 = act49 ? c * 7 : 0;
@@ -166,7 +167,7 @@ __global__ void __launch_bounds__(64 * kDfWaves) df_factor_kernel(DfArgs D) {
 __device__ void col_finish(const ColArgs &C, int lane) {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   __shared__ float dxs[7 * 512];
-  const int32_t *perm = C.plan + C.off[0];
+  const int32_t *perm = C.plan + C.off[kSec_perm];
   const int m = C.m;
   const bool failed =
       __hip_atomic_load(C.flags + kFlagSplitFail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
@@ -236,8 +237,8 @@ __global__ void __launch_bounds__(64) col_backsub_kernel(ColArgs C) {
   __shared__ double Lst[kBsCap * 49], xst[kBsCap * 7];
   const int lane = threadIdx.x;
   const int32_t *pl = C.plan;
-  const int32_t *col_ptr = pl + C.off[1], *col_row = pl + C.off[2], *col_slot = pl + C.off[3],
-                *corder = pl + C.off[29];
+  const int32_t *col_ptr = pl + C.off[kSec_col_ptr], *col_row = pl + C.off[kSec_col_row],
+                *col_slot = pl + C.off[kSec_col_slot], *corder = pl + C.off[kSec_corder];
   const int lane7 = lane < 7 ? lane : 0;
   const int lane49 = lane < 49 ? lane : 0;
   const int base = C.epoch * (C.ncols + (int)gridDim.x);

@@ -133,14 +133,15 @@ int gn_solve_impl(const m3s_gn_args *a, const double *edge_sums, const float *pa
   if (rc0) return rc0;
   rc0 = finish_plan(a, Ly, st);
   if (rc0) return rc0;
-  PlanMeta meta;
+  SolveView view;
   {
     std::lock_guard<std::mutex> g(g_reg_mu);
     auto it = g_reg.find(ws);
     if (it == g_reg.end()) return M3S_EINVAL;  // m3s_gn_prepare not called on this workspace
-    meta = solve_view(it->second);
+    view = solve_view(it->second);
     it->second.epoch++;
   }
+  const PlanRecord &meta = view.plan;
   int rc;
   float *dx = a->dx_out;
   if (meta.sparse) {
@@ -150,7 +151,6 @@ int gn_solve_impl(const m3s_gn_args *a, const double *edge_sums, const float *pa
           edge_sums, edge_sums ? nullptr : partials, chunks, at<int32_t>(ws, Ly.rank_i), a->Twc, fin, stop);
       if ((rc = launch_ok())) return rc;
     }
-    const PlanImage &I = meta.img;
     SparseDev D;
     D.phase = 0;
     D.tail_done = 0;
@@ -158,15 +158,7 @@ int gn_solve_impl(const m3s_gn_args *a, const double *edge_sums, const float *pa
     D.tail_ld = 0;
     D.plan = at<int32_t>(ws, Ly.plan);
     D.plan_len = meta.plan_len;
-    const int64_t offs[kPlanSections] = {
-        I.off_perm,     I.off_col_ptr,      I.off_col_row,  I.off_col_slot, I.off_lev_ptr,
-        I.off_lev_col,  I.off_dtr_ptr,      I.off_dtr_slot, I.off_dtr_p,    I.off_task_lev_ptr,
-        I.off_task_dst, I.off_task_col,     I.off_task_tr_ptr, I.off_tr_a,  I.off_tr_b,
-        I.off_asm_ptr,  I.off_asm_edge,     I.off_g_ptr,    I.off_g_edge,   I.off_ctask_ptr,
-        I.off_items,    I.off_wave_ptr,     I.off_witems,
-        I.off_part_q0,  I.off_part_q1,      I.off_part_tgt, I.off_dpart_ptr, I.off_opart_ptr, I.off_clq,
-        I.off_corder,   I.off_ctask0};
-    for (int q = 0; q < kPlanSections; q++) D.off[q] = (int)offs[q];
+    std::copy(meta.off, meta.off + kPlanSections, D.off);
     D.n_items = meta.n_items;
     D.n_tasks = meta.n_tasks;
     D.n_parts = meta.n_parts;
@@ -182,8 +174,8 @@ int gn_solve_impl(const m3s_gn_args *a, const double *edge_sums, const float *pa
     D.rhs = at<double>(ws, Ly.rhs);
     if (!meta.asm_lds) {  // multi-workgroup assembly into the global factor array
       assemble_slots_kernel<<<dim3((unsigned)(meta.S + meta.m)), dim3(64), 0, st>>>(
-          fin, D.plan, (int)I.off_asm_ptr, (int)I.off_asm_edge, (int)I.off_g_ptr, (int)I.off_g_edge, meta.m,
-          meta.S, D.L, at<double>(ws, Ly.rhs), stop);
+          fin, D.plan, meta.off[kSec_asm_ptr], meta.off[kSec_asm_edge], meta.off[kSec_g_ptr], meta.off[kSec_g_edge],
+          meta.m, meta.S, D.L, at<double>(ws, Ly.rhs), stop);
       if ((rc = launch_ok())) return rc;
     }
     D.Dinv = at<double>(ws, Ly.Dinv);
@@ -199,11 +191,11 @@ int gn_solve_impl(const m3s_gn_args *a, const double *edge_sums, const float *pa
       // -> column back-substitution + step
       ColArgs C;
       C.plan = D.plan;
-      for (int q = 0; q < kPlanSections; q++) C.off[q] = D.off[q];
+      std::copy(meta.off, meta.off + kPlanSections, C.off);
       C.m = meta.m;
       C.c0 = meta.m - meta.nc;
       C.ncols = C.c0;
-      C.epoch = meta.epoch;
+      C.epoch = view.epoch;
       C.L = D.L;
       C.Dinv = D.Dinv;
       C.y = const_cast<double *>(D.rhs);
@@ -225,14 +217,14 @@ int gn_solve_impl(const m3s_gn_args *a, const double *edge_sums, const float *pa
         // every block of the sparse columns and the tail border: one wave-level dataflow
         DfArgs F;
         F.plan = D.plan;
-        for (int q = 0; q < kPlanSections; q++) F.off[q] = D.off[q];
+        std::copy(meta.off, meta.off + kPlanSections, F.off);
         F.items = D.plan + meta.off_dfitems;
         F.n_items = meta.n_dfitems;
         F.n_tasks = meta.n_tasks;
         F.m = meta.m;
         F.c0 = C.c0;
         F.nc = meta.nc;
-        F.epoch = meta.epoch;
+        F.epoch = view.epoch;
         F.L = D.L;
         F.Dinv = D.Dinv;
         F.y = C.y;
@@ -270,7 +262,7 @@ int gn_solve_impl(const m3s_gn_args *a, const double *edge_sums, const float *pa
         if (tail_cyc()) {
           TailSync Y;
           Y.tflag = cs + 2 * (meta.m + 1) + 16 + Ly.slot_cap;
-          Y.epoch = meta.epoch;
+          Y.epoch = view.epoch;
           Y.ypg = T.Wg + (size_t)kTailMaxT * 256;
           Y.LgT = Y.ypg + 16 * kTailMaxT;
           Y.LgG = tail + tail_gran_offset_doubles();
@@ -461,7 +453,7 @@ int gn_full(const m3s_gn_args *a, int mode, void *stream) {
   bool sparse;
   {
     std::lock_guard<std::mutex> g(g_reg_mu);
-    sparse = g_reg.at(a->workspace).sparse;
+    sparse = g_reg.at(a->workspace).plan.sparse;
   }
   CallTiming &CT = call_timing();
   std::unique_lock<std::mutex> tl(CT.mu, std::defer_lock);

@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(64) assemble_slots_kernel(const double *__rest
 struct SparseDev {
   const int32_t *plan;  // flattened plan (global); copied to LDS by the IN_LDS variant
   int plan_len;
-  int off[kPlanSections];  // section offsets, order of m3s_symbolic.h
+  int off[kPlanSections];  // section offsets, indexed by kSec_<name> (m3s_symbolic.h)
   int m, S, levels, n_items;
   int n_tasks, n_parts;  // OFF tasks; PART items (0: no split updates)
   int E, asm_lds;        // asm_lds: assemble in-kernel from fin staged in LDS (else assemble_slots_kernel)
@@ -620,9 +620,10 @@ __device__ __forceinline__ void border_task(int t, int nc, int c0, const int32_t
                                             double *stg, double *Ad = nullptr, int ld = 0,
                                             const int32_t *wflag = nullptr, int want = 0, bool *ok = nullptr) {
   auto put = [&](double *p, double v) { *p = v; };
-  const int32_t *dtr_ptr = pl + off[6], *dtr_slot = pl + off[7], *dtr_p = pl + off[8], *task_dst = pl + off[10],
-                *task_tr_ptr = pl + off[12], *tr_a = pl + off[13], *tr_b = pl + off[14];
-  const int32_t *clq = pl + off[28];
+  const int32_t *dtr_ptr = pl + off[kSec_dtr_ptr], *dtr_slot = pl + off[kSec_dtr_slot], *dtr_p = pl + off[kSec_dtr_p],
+                *task_dst = pl + off[kSec_task_dst], *task_tr_ptr = pl + off[kSec_task_tr_ptr],
+                *tr_a = pl + off[kSec_tr_a], *tr_b = pl + off[kSec_tr_b];
+  const int32_t *clq = pl + off[kSec_clq];
   const int32_t *ct0 = clq + 2, *bend = clq + 2 + nc;
   int ci = 0, rem = t;  // t -> (ci, ri), ci <= ri < nc, column-major
   while (rem >= nc - ci) rem -= nc - ci, ci++;

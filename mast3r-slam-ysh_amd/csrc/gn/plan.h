@@ -1,15 +1,19 @@
 // gn/plan.h — part of the m3s_gn.hip translation unit (not a stand-alone header).
-// From edge ids to a plan on the device: PlanMeta and the workspace registry,
-// pinned staging, the plan cache, set_knob, build_plan_meta, build_eorder,
-// upload_plan, gn_prepare_impl (host prepare), finish_plan / host_finish and
-// gn_prepare_async (the prologue launch).
+// From edge ids to a plan on the device: PlanRecord (the one declaration of
+// what a solve launch reads of a plan), PlanMeta and the workspace registry,
+// pinned staging, the plan cache (find_cached_plan), set_knob,
+// build_plan_meta, build_eorder, upload_plan, adopt_plan, gn_prepare_impl
+// (host prepare), finish_plan / host_finish, gn_prepare_async (the prologue
+// launch) and gn_release_impl.
 // Relies on gn/layout.h (Layout / gn_layout), gn/llt_blocks.h
 // (kStageDoubles, kSplitUpdates), gn/prologue.h (the call prologue), gn/args.h
 // (S, launch_ok) and gn/knobs.h; declares set_lds_attributes_once, which
 // gn/iterate.h defines.
 
-struct PlanMeta {
-  int epoch = 0;  // solve launches since m3s_gn_prepare (column-task flags / tickets)
+// What a solve launch reads of a plan. Built once per edge set
+// (build_plan_meta), kept by the plan cache and copied whole: a field added
+// here reaches the cold, the cached and the host-prepare path alike.
+struct PlanRecord {
   bool sparse = false;
   int store = 0;  // sparse_llt_kernel<STORE>
   bool asm_lds = false;  // LDS factor with room for the staged fin blocks: assembly in the LLT kernel
@@ -18,16 +22,19 @@ struct PlanMeta {
   int nnz = 0;  // off-diagonal blocks (col_ptr[m])
   int off_dfitems = 0, n_dfitems = 0;  // df_factor_kernel dispatch list (appended to the plan image)
   int n_dfsparse = 0;                  // its sparse-column items (the border items follow)
-  PlanImage img;  // offsets (data vector cleared after upload)
-  // linearize state of this solve call: edge ranks, the task table of the
-  // edge range last linearized (host copy stays alive for the async upload)
-  // and whether that range's planes are stored
+  int off[kPlanSections] = {};         // section offsets into the image (PlanImage::off)
+};
+static_assert(std::is_trivially_copyable<PlanRecord>::value, "copied under the registry lock");
+
+// The registry entry of a solve call: its plan, the plan's image, and the
+// state of this call alone. Every prepare starts from a fresh one.
+struct PlanMeta {
+  PlanRecord plan;
+  std::vector<int32_t> h_plan;  // flattened plan image (host copy of the upload)
+  int epoch = 0;  // solve launches since m3s_gn_prepare (column-task flags / tickets)
+  // linearize state of this solve call: edge ranks, the edge range last
+  // linearized and whether that range's planes are stored
   std::vector<int32_t> rj, h_ri;   // edge ranks (host copies of the uploaded arrays)
-  std::vector<int32_t> h_plan;     // flattened plan (host copy of the upload)
-  int32_t h_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int32_t h_flags[64] = {0};
-  bool has_K = false;
-  float K4[4] = {0.f, 0.f, 0.f, 0.f};  // fx, fy, cx, cy (calib; read once per call)
   int64_t range_b = -1, range_e = -1;  // the edge range last linearized
   bool order_ok = false;               // its edge order is in the workspace (Layout::eorder)
   bool planes_ok = false;
@@ -36,7 +43,6 @@ struct PlanMeta {
   // the counters hold arrivals of another range or of a drop-in call
   uint32_t cnt_arr = 0;
   bool cnt_ok = true;
-  std::vector<int32_t> eorder;         // host copy of the full range's order (host prepare)
   // the symbolic plan of this call is built by its first solve (cache miss at
   // prepare): the host analysis then overlaps the first linearize kernel
   bool plan_pending = false;
@@ -47,28 +53,21 @@ struct PlanMeta {
   int slot = -1;
 };
 
-// What a solve launch reads of the registry entry: the scalars and plan
-// offsets, not the host vectors (ranks, task tables, plan image) that the
-// entry keeps alive for queued uploads.
-PlanMeta solve_view(const PlanMeta &M) {
-  PlanMeta v;
-  v.epoch = M.epoch, v.sparse = M.sparse, v.store = M.store, v.asm_lds = M.asm_lds, v.lds_bytes = M.lds_bytes;
-  v.m = M.m, v.S = M.S, v.levels = M.levels, v.plan_len = M.plan_len, v.n_items = M.n_items;
-  v.n_tasks = M.n_tasks, v.n_parts = M.n_parts, v.nc = M.nc, v.off_dfitems = M.off_dfitems;
-  v.n_dfitems = M.n_dfitems;
-  v.n_dfsparse = M.n_dfsparse;
-  v.nnz = M.nnz;
-  v.img = M.img;  // offsets (its data vector is empty in the registry)
-  v.plan_pending = M.plan_pending;
-  return v;
-}
+// What a solve launch reads of the registry entry: the plan record and the
+// epoch, not the host vectors (ranks, plan image) that the entry keeps alive
+// for queued uploads.
+struct SolveView {
+  PlanRecord plan;
+  int epoch;
+};
+SolveView solve_view(const PlanMeta &M) { return {M.plan, M.epoch}; }
 // Host registry of the per-call plan (keyed by workspace): the stepwise API
 // calls prepare and solve separately.
 std::mutex g_reg_mu;
 std::unordered_map<const void *, PlanMeta> g_reg;
 
 // Pinned host staging of the per-call transfers (gn_prepare_impl: the D2H
-// reads of K, ii, jj and ONE H2D upload of flags | ranks | task table | plan;
+// reads of ii, jj and ONE H2D upload of flags | ranks | task table | plan;
 // finish_plan: a deferred plan; gn_linearize_impl: a sharded rank's task
 // table). Pageable copies were one staged, host-synchronous transfer each
 // (~7 per call); an event per buffer guards it until the copy that reads it
@@ -156,17 +155,37 @@ void set_lds_attributes_once();
 
 // Host symbolic plans of recent edge sets (the same factor graph is usually
 // solved many times: every keyframe's local/global optimisation, every bench
-// step). Keyed by (N, HW, E, dense override, remapped ranks).
+// step). Keyed by (N, HW, E, dense override, remapped ranks). An entry is its
+// key, the plan record and the image: no part of the call that built it.
 struct PlanCacheEntry {
   int64_t N = 0, HW = 0, E = 0;
   bool dense = false;
   int tail_min = 0;  // dense_tail_min() the plan was built with
   std::vector<int32_t> ri, rj;
-  PlanMeta meta;
+  PlanRecord plan;
+  std::vector<int32_t> image;
 };
 std::mutex g_cache_mu;
 std::vector<PlanCacheEntry> g_cache;  // most recent first
 constexpr size_t kPlanCacheSize = 4;
+
+// The cached plan of this edge set, moved to the front of the cache.
+bool find_cached_plan(const m3s_gn_args *a, bool force_dense, const std::vector<int32_t> &ri,
+                      const std::vector<int32_t> &rj, PlanRecord &plan, std::vector<int32_t> &image) {
+  if (!plan_cache_enabled()) return false;
+  std::lock_guard<std::mutex> g(g_cache_mu);
+  for (size_t q = 0; q < g_cache.size(); q++) {
+    const PlanCacheEntry &C = g_cache[q];
+    if (C.N == a->N && C.HW == a->HW && C.E == a->E && C.dense == force_dense &&
+        C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
+      plan = C.plan;
+      image = C.image;
+      std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
+      return true;
+    }
+  }
+  return false;
+}
 
 // m3s_set_knob: the previous value, or -(1 << 30) for a name this build does
 // not know. A plan-shaping knob set to a different value drops the plan cache.
@@ -187,7 +206,8 @@ int set_knob(const char *name, int value) {
 // Symbolic plan + LDS budget + full-range task table for remapped ranks.
 PlanMeta build_plan_meta(const m3s_gn_args *a, const Layout &Ly, const std::vector<int32_t> &ri,
                          const std::vector<int32_t> &rj, bool force_dense) {
-  PlanMeta meta;
+  PlanMeta built;
+  PlanRecord &R = built.plan;
   const int64_t E = a->E;
   if (a->N > 1) {
     SparsePlan P;
@@ -206,26 +226,26 @@ PlanMeta build_plan_meta(const m3s_gn_args *a, const Layout &Ly, const std::vect
     flatten_plan(P, img);
     // df_factor_kernel's dispatch list: the sparse columns in level order,
     // DIAG(k) then the OFF tasks of column k, then the dense-tail border tasks
-    meta.off_dfitems = (int)img.data.size();
+    R.off_dfitems = (int)img.data.size();
     for (int32_t k : P.corder) {
       img.data.push_back(-1 - k);
       for (int q = 0; q < P.col_ptr[k + 1] - P.col_ptr[k]; q++) img.data.push_back(P.ctask0[k] + q);
     }
-    meta.n_dfsparse = (int)img.data.size() - meta.off_dfitems;
+    R.n_dfsparse = (int)img.data.size() - R.off_dfitems;
     for (int b = 0; b < P.nc * (P.nc + 1) / 2; b++) img.data.push_back((int32_t)P.task_dst.size() + b);
-    meta.n_dfitems = (int)img.data.size() - meta.off_dfitems;
+    R.n_dfitems = (int)img.data.size() - R.off_dfitems;
     const bool fits = (int64_t)img.data.size() <= Ly.plan_cap && P.S <= Ly.slot_cap;
     if (fits && !force_dense) {
-      meta.sparse = true;
-      meta.m = P.m;
-      meta.S = P.S;
-      meta.levels = P.levels;
-      meta.plan_len = (int)img.data.size();
-      meta.n_items = (int)P.items.size();
-      meta.n_tasks = (int)P.task_dst.size();
-      meta.n_parts = (int)P.part_q0.size();
-      meta.nc = P.nc;
-      meta.nnz = P.col_ptr.empty() ? 0 : P.col_ptr[P.m];
+      R.sparse = true;
+      R.m = P.m;
+      R.S = P.S;
+      R.levels = P.levels;
+      R.plan_len = (int)img.data.size();
+      R.n_items = (int)P.items.size();
+      R.n_tasks = (int)P.task_dst.size();
+      R.n_parts = (int)P.part_q0.size();
+      R.nc = P.nc;
+      R.nnz = P.col_ptr.empty() ? 0 : P.col_ptr[P.m];
       // LDS plan of sparse_llt_kernel<STORE>: flags always, factor + W + y if
       // they fit, the plan too if it fits as well; else global factor with
       // per-wave stage areas
@@ -236,39 +256,38 @@ PlanMeta build_plan_meta(const m3s_gn_args *a, const Layout &Ly, const std::vect
       const size_t stage_bytes = sizeof(double) * 16 * (size_t)kStageDoubles;
       const size_t fin_bytes = sizeof(double) * kFin * (size_t)E;
       if (fac_bytes + plan_bytes + flags_bytes <= kMaxLdsBytes) {
-        meta.store = 1;
-        meta.lds_bytes = fac_bytes + plan_bytes + flags_bytes;
+        R.store = 1;
+        R.lds_bytes = fac_bytes + plan_bytes + flags_bytes;
       } else if (fac_bytes + flags_bytes <= kMaxLdsBytes) {
-        meta.store = 2;
-        meta.lds_bytes = fac_bytes + flags_bytes;
+        R.store = 2;
+        R.lds_bytes = fac_bytes + flags_bytes;
       }
-      if (meta.store != 0 && meta.lds_bytes + fin_bytes <= kMaxLdsBytes) {
-        meta.asm_lds = true;
-        meta.lds_bytes += fin_bytes;
+      if (R.store != 0 && R.lds_bytes + fin_bytes <= kMaxLdsBytes) {
+        R.asm_lds = true;
+        R.lds_bytes += fin_bytes;
       }
-      if (meta.store == 0) {
-        meta.store = 0;
-        meta.lds_bytes = sizeof(double) * (size_t)P.m * 7 + flags_bytes + stage_bytes;
-        if (meta.lds_bytes > kMaxLdsBytes) meta.sparse = false;  // dense fallback
+      if (R.store == 0) {
+        R.store = 0;
+        R.lds_bytes = sizeof(double) * (size_t)P.m * 7 + flags_bytes + stage_bytes;
+        if (R.lds_bytes > kMaxLdsBytes) R.sparse = false;  // dense fallback
       }
-      meta.h_plan = std::move(img.data);
-      img.data.clear();
-      meta.img = img;
+      std::copy(img.off, img.off + kPlanSections, R.off);
+      built.h_plan = std::move(img.data);
     }
   }
   (void)E;
-  return meta;
+  return built;
 }
 
 // The per-call flag state the solve kernels of a plan rely on: the column-
 // task / dataflow / dense-tail epoch flags live only on the global-factor
 // path (the LDS-resident factors keep theirs in LDS), and no tagged granule
 // of an earlier call may match this call's epochs.
-bool reset_plan_flags(const PlanMeta &M, const Layout &Ly, void *ws, hipStream_t st) {
+bool reset_plan_flags(const PlanRecord &R, const Layout &Ly, void *ws, hipStream_t st) {
   bool ok = true;
-  if (!(M.sparse && M.store != 0))
+  if (!(R.sparse && R.store != 0))
     ok &= hipMemsetAsync(at<int32_t>(ws, Ly.colsync), 0, Ly.tail - Ly.colsync, st) == hipSuccess;
-  if (M.nc > 0)
+  if (R.nc > 0)
     ok &= hipMemsetAsync(at<double>(ws, Ly.tail) + tail_gran_offset_doubles(), 0,
                          sizeof(double) * (tail_scratch_doubles() - tail_gran_offset_doubles()), st) == hipSuccess;
   return ok;
@@ -279,7 +298,7 @@ bool reset_plan_flags(const PlanMeta &M, const Layout &Ly, void *ws, hipStream_t
 // it. Callers have waited for every earlier launch on `st` (the prologue's
 // event or a stream sync), so nothing still running there reads `dst`.
 bool upload_plan(Staging *SG, PlanMeta &M, char *dst, hipStream_t st) {
-  if (!(M.sparse && !M.h_plan.empty())) return true;
+  if (!(M.plan.sparse && !M.h_plan.empty())) return true;
   const size_t nb = sizeof(int32_t) * M.h_plan.size();
   if (SG->plan_pending && hipEventSynchronize(SG->plan_ev) != hipSuccess) return false;
   SG->plan_pending = false;
@@ -300,25 +319,41 @@ bool upload_plan(Staging *SG, PlanMeta &M, char *dst, hipStream_t st) {
 // df_factor_kernel's dispatch list instead.
 void apply_drop_item(PlanMeta &M) {
   const int d = drop_item_knob();
-  if (d < 0 || !M.sparse || M.h_plan.empty()) return;
-  if (M.store == 0 && M.n_dfitems > 0) {
-    int32_t *di = M.h_plan.data() + M.off_dfitems;
-    if (d < M.n_dfitems) {
-      for (int t = d; t + 1 < M.n_dfitems; t++) di[t] = di[t + 1];
-      M.n_dfitems -= 1;
+  PlanRecord &R = M.plan;
+  if (d < 0 || !R.sparse || M.h_plan.empty()) return;
+  if (R.store == 0 && R.n_dfitems > 0) {
+    int32_t *di = M.h_plan.data() + R.off_dfitems;
+    if (d < R.n_dfitems) {
+      for (int t = d; t + 1 < R.n_dfitems; t++) di[t] = di[t + 1];
+      R.n_dfitems -= 1;
     }
     return;
   }
-  if (M.img.off_wave_ptr >= (int64_t)M.h_plan.size()) return;
-  int32_t *wp = M.h_plan.data() + M.img.off_wave_ptr, *wi = M.h_plan.data() + M.img.off_witems;
+  if (R.off[kSec_wave_ptr] >= (int64_t)M.h_plan.size()) return;
+  int32_t *wp = M.h_plan.data() + R.off[kSec_wave_ptr], *wi = M.h_plan.data() + R.off[kSec_witems];
   if (d < wp[1]) {
     for (int t = d; t + 1 < wp[1]; t++) wi[t] = wi[t + 1];
     wp[1] -= 1;
   }
 }
 
+// A plan becomes the plan of the call behind registry entry M (a deferred
+// plan just built, finish_plan; a cached one, host_finish): record and image
+// into the entry, the per-plan flag resets, the test hook, the upload.
+// Caller holds g_stage_mu and g_reg_mu.
+int adopt_plan(Staging *SG, PlanMeta &M, const PlanRecord &plan, std::vector<int32_t> &&image, const Layout &Ly,
+               void *ws, hipStream_t st) {
+  M.plan = plan;
+  M.h_plan = std::move(image);
+  M.plan_pending = false;
+  bool ok = reset_plan_flags(M.plan, Ly, ws, st);
+  apply_drop_item(M);
+  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
+  return ok ? M3S_OK : M3S_ELAUNCH;
+}
+
 // The host prepare, per solve call (the reference's _unique / searchsorted
-// also synchronise): read ii/jj (+ K) once — the call's only host sync — rank the
+// also synchronise): read ii/jj once — the call's only host sync — rank the
 // ids, fetch the plan (or defer it to the first solve) and enqueue ONE
 // upload of everything the launches read (pinned staging, above).
 int gn_prepare_impl(const m3s_gn_args *a, hipStream_t st) {
@@ -330,13 +365,8 @@ int gn_prepare_impl(const m3s_gn_args *a, hipStream_t st) {
   if (SG->pending && hipEventSynchronize(SG->ev) != hipSuccess) return M3S_ELAUNCH;
   SG->pending = false;
   const int64_t E = a->E;
-  if (!pinned_reserve(SG->down, SG->down_cap, 64 + 2 * sizeof(int64_t) * (size_t)E)) return M3S_ELAUNCH;
-  float *hK = reinterpret_cast<float *>(SG->down);  // calib intrinsics, read with ii/jj
-  int64_t *hii = reinterpret_cast<int64_t *>(SG->down + 64), *hjj = hii + E;
-  for (int q = 0; q < 9; q++) hK[q] = 0.f;
-  if (a->mode == M3S_MODE_CALIB &&
-      hipMemcpyAsync(hK, a->K, sizeof(float) * 9, hipMemcpyDeviceToHost, st) != hipSuccess)
-    return M3S_ELAUNCH;
+  if (!pinned_reserve(SG->down, SG->down_cap, 2 * sizeof(int64_t) * (size_t)E)) return M3S_ELAUNCH;
+  int64_t *hii = reinterpret_cast<int64_t *>(SG->down), *hjj = hii + E;
   if (a->N > 1 && a->dx_out && hipMemsetAsync(a->dx_out, 0, sizeof(float) * 7 * (a->N - 1), st) != hipSuccess)
     return M3S_ELAUNCH;
   if (E > 0 && hipMemcpyAsync(hii, a->ii, sizeof(int64_t) * E, hipMemcpyDeviceToHost, st) != hipSuccess)
@@ -349,72 +379,52 @@ int gn_prepare_impl(const m3s_gn_args *a, hipStream_t st) {
   const bool bad = nu > a->N;
   const bool force_dense = force_dense_knob();
   PlanMeta meta;
-  bool hit = false;
-  if (!bad && plan_cache_enabled()) {
-    std::lock_guard<std::mutex> g(g_cache_mu);
-    for (size_t q = 0; q < g_cache.size(); q++) {
-      const PlanCacheEntry &C = g_cache[q];
-      if (C.N == a->N && C.HW == a->HW && C.E == E && C.dense == force_dense &&
-          C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
-        meta = C.meta;
-        std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
-        hit = true;
-        break;
-      }
-    }
-  }
-  if (hit && E > 0 && meta.eorder.empty()) build_eorder(meta.rj, 0, E, meta.eorder);  // cached by the prologue path
+  const bool hit = !bad && find_cached_plan(a, force_dense, ri, rj, meta.plan, meta.h_plan);
   if (!hit) {
-    // ranks and the full-range task table now (the first linearize needs
-    // them); the symbolic plan is built by the first solve of this call,
-    // while the first linearize kernel runs (finish_plan)
-    meta.h_ri = ri;
-    meta.rj = rj;
-    if (E > 0) build_eorder(meta.rj, 0, E, meta.eorder);
-    meta.sparse = !bad && !force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
+    // the symbolic plan is built by the first solve of this call, while the
+    // first linearize kernel runs (finish_plan); `sparse` is the expected
+    // outcome until then (the dense path reads partials either way)
+    meta.plan.sparse = !bad && !force_dense && a->N > 1;
     meta.plan_pending = !bad && a->N > 1;
-    meta.force_dense = force_dense;
   }
-  for (int q = 0; q < 8; q++) meta.h_info[q] = 0;
-  for (int q = 0; q < 64; q++) meta.h_flags[q] = 0;
-  meta.h_info[M3S_INFO_N_UNIQUE] = nu;
-  if (bad) meta.h_info[M3S_INFO_BAD_EDGE] = 1, meta.h_flags[kFlagStop] = 1;
-  if (a->mode == M3S_MODE_CALIB) {  // K row-major: fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]
-    meta.has_K = true;
-    meta.K4[0] = hK[0], meta.K4[1] = hK[4], meta.K4[2] = hK[2], meta.K4[3] = hK[5];
-  }
-  meta.planes_ok = false;
+  meta.force_dense = force_dense;
+  // ranks and the full range's edge order now (the first linearize needs them)
+  std::vector<int32_t> eorder;
+  if (E > 0) build_eorder(rj, 0, E, eorder);
+  meta.h_ri = std::move(ri), meta.rj = std::move(rj);
+  int32_t h_info[8] = {0}, h_flags[64] = {0};
+  h_info[M3S_INFO_N_UNIQUE] = nu;
+  if (bad) h_info[M3S_INFO_BAD_EDGE] = 1, h_flags[kFlagStop] = 1;
   meta.range_b = 0, meta.range_e = E, meta.order_ok = E > 0;
-  if (meta.sparse && !meta.plan_pending && meta.lds_bytes > 64 * 1024) set_lds_attributes_once();
+  if (meta.plan.sparse && !meta.plan_pending && meta.plan.lds_bytes > 64 * 1024) set_lds_attributes_once();
   std::lock_guard<std::mutex> g(g_reg_mu);
   PlanMeta &M = g_reg[ws];
   M = std::move(meta);
   bool ok = true;
-  if (!M.plan_pending) ok &= reset_plan_flags(M, Ly, ws, st);
-  M.epoch = 0;
+  if (!M.plan_pending) ok &= reset_plan_flags(M.plan, Ly, ws, st);
   if (!M.plan_pending) apply_drop_item(M);
   // one upload: flags | rank_i | rank_j | edge counters | edge order [| plan] (the
   // layout keeps them in this order), then info (the caller's tensor) from
   // the same buffer
-  const bool with_plan = M.sparse && !M.plan_pending && !M.h_plan.empty();
+  const bool with_plan = M.plan.sparse && !M.plan_pending && !M.h_plan.empty();
   const bool with_tasks = E > 0;
   size_t n_up = with_plan ? Ly.plan - Ly.flags + sizeof(int32_t) * M.h_plan.size()
-                          : with_tasks ? Ly.eorder - Ly.flags + sizeof(int32_t) * M.eorder.size()
+                          : with_tasks ? Ly.eorder - Ly.flags + sizeof(int32_t) * eorder.size()
                                        : Ly.edge_cnt - Ly.flags + edge_cnt_bytes(E);
   n_up = align_up(n_up, 16);
-  if (!pinned_reserve(SG->up, SG->up_cap, n_up + sizeof M.h_info)) return M3S_ELAUNCH;
+  if (!pinned_reserve(SG->up, SG->up_cap, n_up + sizeof h_info)) return M3S_ELAUNCH;
   char *up = SG->up;
-  memcpy(up, M.h_flags, sizeof M.h_flags);
+  memcpy(up, h_flags, sizeof h_flags);
   memset(up + (Ly.edge_cnt - Ly.flags), 0, edge_cnt_bytes(E));  // the fused finalize's counters
   if (E > 0) {
     memcpy(up + (Ly.rank_i - Ly.flags), M.h_ri.data(), sizeof(int32_t) * E);
     memcpy(up + (Ly.rank_j - Ly.flags), M.rj.data(), sizeof(int32_t) * E);
   }
-  if (with_tasks) memcpy(up + (Ly.eorder - Ly.flags), M.eorder.data(), sizeof(int32_t) * M.eorder.size());
+  if (with_tasks) memcpy(up + (Ly.eorder - Ly.flags), eorder.data(), sizeof(int32_t) * eorder.size());
   if (with_plan) memcpy(up + (Ly.plan - Ly.flags), M.h_plan.data(), sizeof(int32_t) * M.h_plan.size());
-  memcpy(up + n_up, M.h_info, sizeof M.h_info);
+  memcpy(up + n_up, h_info, sizeof h_info);
   ok &= hipMemcpyAsync(at<char>(ws, Ly.flags), up, n_up, hipMemcpyHostToDevice, st) == hipSuccess;
-  ok &= hipMemcpyAsync(a->info, up + n_up, sizeof M.h_info, hipMemcpyHostToDevice, st) == hipSuccess;
+  ok &= hipMemcpyAsync(a->info, up + n_up, sizeof h_info, hipMemcpyHostToDevice, st) == hipSuccess;
   ok &= hipEventRecord(SG->ev, st) == hipSuccess;
   SG->pending = ok;
   return ok ? M3S_OK : M3S_ELAUNCH;
@@ -438,41 +448,29 @@ int finish_plan(const m3s_gn_args *a, const Layout &Ly, hipStream_t st) {
     force_dense = it->second.force_dense;
   }
   PlanMeta built = build_plan_meta(a, Ly, ri, rj, force_dense);
-  if (built.sparse && built.lds_bytes > 64 * 1024) set_lds_attributes_once();
+  if (built.plan.sparse && built.plan.lds_bytes > 64 * 1024) set_lds_attributes_once();
   std::lock_guard<std::mutex> stage_lock(g_stage_mu);
   Staging *SG = stage_for_device();
   if (!SG) return M3S_ELAUNCH;
   if (SG->plan_pending && hipEventSynchronize(SG->plan_ev) != hipSuccess) return M3S_ELAUNCH;
   SG->plan_pending = false;
   std::lock_guard<std::mutex> g(g_reg_mu);
-  PlanMeta &M = g_reg[ws];
-  M.sparse = built.sparse, M.store = built.store, M.asm_lds = built.asm_lds, M.lds_bytes = built.lds_bytes;
-  M.m = built.m, M.S = built.S, M.levels = built.levels, M.plan_len = built.plan_len;
-  M.n_items = built.n_items, M.n_tasks = built.n_tasks, M.n_parts = built.n_parts, M.nc = built.nc;
-  M.off_dfitems = built.off_dfitems, M.n_dfitems = built.n_dfitems, M.nnz = built.nnz;
-  M.n_dfsparse = built.n_dfsparse;
-  M.img = built.img;
-  M.h_plan = std::move(built.h_plan);
-  M.plan_pending = false;
   if (plan_cache_enabled()) {
     PlanCacheEntry C;
     C.N = a->N, C.HW = a->HW, C.E = a->E, C.dense = force_dense, C.ri = ri, C.rj = rj;
     C.tail_min = dense_tail_min();
-    C.meta = M;
+    C.plan = built.plan, C.image = built.h_plan;
     std::lock_guard<std::mutex> gc(g_cache_mu);
     g_cache.insert(g_cache.begin(), std::move(C));
     if (g_cache.size() > kPlanCacheSize) g_cache.pop_back();
   }
-  bool ok = reset_plan_flags(M, Ly, ws, st);
-  apply_drop_item(M);
-  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
-  return ok ? M3S_OK : M3S_ELAUNCH;
+  return adopt_plan(SG, g_reg[ws], built.plan, std::move(built.h_plan), Ly, ws, st);
 }
 
 // The host half of an async prepare (gn_prepare_async), at the first point a
 // call needs its ids on the host (its first solve, or a sharded rank's edge
 // range): wait for the prologue (normally long done: the first linearize is
-// queued behind it), read ii / jj / K from the pinned slot, rank the ids on
+// queued behind it), read ii / jj from the pinned slot, rank the ids on
 // the host (the plan and its cache key need them), and fetch the cached plan;
 // a miss leaves the plan to finish_plan. The linearize state of the entry
 // (range, task table, planes) is the prologue's and stays.
@@ -488,14 +486,12 @@ int host_finish(const m3s_gn_args *a, hipStream_t st) {
   }
   const int64_t E = a->E;
   std::vector<int64_t> hii((size_t)E), hjj((size_t)E);
-  float hK[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   {
     std::lock_guard<std::mutex> stage_lock(g_stage_mu);
     Staging *SG = stage_for_device();
     if (!SG || slot < 0 || slot >= (int)SG->slots.size()) return M3S_ELAUNCH;
     DownSlot &D = SG->slots[slot];
     if (hipEventSynchronize(D.ev) != hipSuccess) return M3S_ELAUNCH;
-    if (a->mode == M3S_MODE_CALIB) memcpy(hK, D.p, sizeof hK);
     if (E > 0) {
       memcpy(hii.data(), D.p + 64, sizeof(int64_t) * (size_t)E);
       memcpy(hjj.data(), D.p + 64 + sizeof(int64_t) * (size_t)E, sizeof(int64_t) * (size_t)E);
@@ -511,22 +507,10 @@ int host_finish(const m3s_gn_args *a, hipStream_t st) {
     std::lock_guard<std::mutex> g(g_reg_mu);
     force_dense = g_reg.at(ws).force_dense;
   }
-  PlanMeta hitm;
-  bool hit = false;
-  if (!bad && plan_cache_enabled()) {
-    std::lock_guard<std::mutex> g(g_cache_mu);
-    for (size_t q = 0; q < g_cache.size(); q++) {
-      const PlanCacheEntry &C = g_cache[q];
-      if (C.N == a->N && C.HW == a->HW && C.E == E && C.dense == force_dense &&
-          C.tail_min == dense_tail_min() && C.ri == ri && C.rj == rj) {
-        hitm = C.meta;
-        std::rotate(g_cache.begin(), g_cache.begin() + q, g_cache.begin() + q + 1);
-        hit = true;
-        break;
-      }
-    }
-  }
-  if (hit && hitm.sparse && hitm.lds_bytes > 64 * 1024) set_lds_attributes_once();
+  PlanRecord plan;
+  std::vector<int32_t> image;
+  const bool hit = !bad && find_cached_plan(a, force_dense, ri, rj, plan, image);
+  if (hit && plan.sparse && plan.lds_bytes > 64 * 1024) set_lds_attributes_once();
   std::lock_guard<std::mutex> stage_lock(g_stage_mu);
   Staging *SG = stage_for_device();
   if (!SG) return M3S_ELAUNCH;
@@ -534,24 +518,12 @@ int host_finish(const m3s_gn_args *a, hipStream_t st) {
   PlanMeta &M = g_reg[ws];
   M.host_pending = false, M.slot = -1;
   M.h_ri = std::move(ri), M.rj = std::move(rj);
-  M.K4[0] = hK[0], M.K4[1] = hK[4], M.K4[2] = hK[2], M.K4[3] = hK[5];
   if (bad) {
-    M.sparse = false, M.plan_pending = false;
+    M.plan.sparse = false, M.plan_pending = false;
     return M3S_OK;
   }
   if (!hit) return M3S_OK;  // plan_pending: finish_plan builds it
-  M.sparse = hitm.sparse, M.store = hitm.store, M.asm_lds = hitm.asm_lds, M.lds_bytes = hitm.lds_bytes;
-  M.m = hitm.m, M.S = hitm.S, M.levels = hitm.levels, M.plan_len = hitm.plan_len;
-  M.n_items = hitm.n_items, M.n_tasks = hitm.n_tasks, M.n_parts = hitm.n_parts, M.nc = hitm.nc;
-  M.off_dfitems = hitm.off_dfitems, M.n_dfitems = hitm.n_dfitems, M.nnz = hitm.nnz;
-  M.n_dfsparse = hitm.n_dfsparse;
-  M.img = hitm.img;
-  M.h_plan = std::move(hitm.h_plan);
-  M.plan_pending = false;
-  bool ok = reset_plan_flags(M, Ly, ws, st);
-  apply_drop_item(M);
-  ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
-  return ok ? M3S_OK : M3S_ELAUNCH;
+  return adopt_plan(SG, M, plan, std::move(image), Ly, ws, st);
 }
 
 // Prepare a call without a host round trip: one prologue kernel on the stream
@@ -589,9 +561,8 @@ int gn_prepare_async(const m3s_gn_args *a, hipStream_t st) {
   }
   PlanMeta meta;
   meta.host_pending = true, meta.slot = slot;
-  meta.has_K = a->mode == M3S_MODE_CALIB;
   meta.force_dense = force_dense_knob();
-  meta.sparse = !meta.force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
+  meta.plan.sparse = !meta.force_dense && a->N > 1;  // the expected outcome (the dense path reads partials either way)
   meta.plan_pending = a->N > 1;
   meta.range_b = 0, meta.range_e = E, meta.order_ok = E > 0;
   std::lock_guard<std::mutex> g(g_reg_mu);
@@ -599,6 +570,21 @@ int gn_prepare_async(const m3s_gn_args *a, hipStream_t st) {
   if (M.host_pending && M.slot >= 0 && M.slot < (int)SG->slots.size() && M.slot != slot)
     SG->slots[M.slot].busy = false;  // a re-prepare of a workspace whose ids were never read
   M = std::move(meta);
-  M.epoch = 0;
+  return M3S_OK;
+}
+
+// m3s_gn_release: drop the registry entry of a workspace. No stream sync:
+// every queued upload reads pinned staging, not the entry.
+int gn_release_impl(const m3s_gn_args *a) {
+  if (!a || !a->workspace) return M3S_EINVAL;
+  std::lock_guard<std::mutex> stage_lock(g_stage_mu);  // (lock order: staging, then registry)
+  std::lock_guard<std::mutex> g(g_reg_mu);
+  auto it = g_reg.find(a->workspace);
+  if (it == g_reg.end()) return M3S_OK;
+  if (it->second.host_pending && it->second.slot >= 0) {  // ids never read: free the slot (its
+    Staging *SG = stage_for_device();                      // event guards the reuse)
+    if (SG && it->second.slot < (int)SG->slots.size()) SG->slots[it->second.slot].busy = false;
+  }
+  g_reg.erase(it);
   return M3S_OK;
 }

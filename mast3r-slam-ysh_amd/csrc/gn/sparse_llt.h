@@ -46,14 +46,18 @@ __global__ void __launch_bounds__(1024) sparse_llt_kernel(SparseDev D) {
   int32_t *after_y = reinterpret_cast<int32_t *>(y + (size_t)m * 7);
   // index arrays: LDS copy (STORE 1) or global
   const int32_t *pl = STORE == 1 ? after_y : D.plan;
-  const int32_t *perm = pl + D.off[0], *col_ptr = pl + D.off[1], *col_row = pl + D.off[2],
-                *col_slot = pl + D.off[3], *lev_col = pl + D.off[5], *dtr_ptr = pl + D.off[6],
-                *dtr_slot = pl + D.off[7], *dtr_p = pl + D.off[8], *task_dst = pl + D.off[10],
-                *task_col = pl + D.off[11], *task_tr_ptr = pl + D.off[12], *tr_a = pl + D.off[13],
-                *tr_b = pl + D.off[14], *asm_ptr = pl + D.off[15], *asm_edge = pl + D.off[16],
-                *g_ptr = pl + D.off[17], *g_edge = pl + D.off[18], *wave_ptr = pl + D.off[21],
-                *witems = pl + D.off[22], *part_q0 = pl + D.off[23], *part_q1 = pl + D.off[24],
-                *part_tgt = pl + D.off[25], *dpart_ptr = pl + D.off[26], *opart_ptr = pl + D.off[27];
+  const int32_t *perm = pl + D.off[kSec_perm], *col_ptr = pl + D.off[kSec_col_ptr],
+                *col_row = pl + D.off[kSec_col_row], *col_slot = pl + D.off[kSec_col_slot],
+                *lev_col = pl + D.off[kSec_lev_col], *dtr_ptr = pl + D.off[kSec_dtr_ptr],
+                *dtr_slot = pl + D.off[kSec_dtr_slot], *dtr_p = pl + D.off[kSec_dtr_p],
+                *task_dst = pl + D.off[kSec_task_dst], *task_col = pl + D.off[kSec_task_col],
+                *task_tr_ptr = pl + D.off[kSec_task_tr_ptr], *tr_a = pl + D.off[kSec_tr_a],
+                *tr_b = pl + D.off[kSec_tr_b], *asm_ptr = pl + D.off[kSec_asm_ptr],
+                *asm_edge = pl + D.off[kSec_asm_edge], *g_ptr = pl + D.off[kSec_g_ptr],
+                *g_edge = pl + D.off[kSec_g_edge], *wave_ptr = pl + D.off[kSec_wave_ptr],
+                *witems = pl + D.off[kSec_witems], *part_q0 = pl + D.off[kSec_part_q0],
+                *part_q1 = pl + D.off[kSec_part_q1], *part_tgt = pl + D.off[kSec_part_tgt],
+                *dpart_ptr = pl + D.off[kSec_dpart_ptr], *opart_ptr = pl + D.off[kSec_opart_ptr];
   const int n_tasks = D.n_tasks;
   const bool split = D.n_parts > 0;
   // completion flags: sdone[slot] (factor block final; diagonal slot k also
@@ -275,7 +279,7 @@ __global__ void __launch_bounds__(1024) sparse_llt_kernel(SparseDev D) {
     for (int q = tid; q < D.nc; q += 1024) done2[m - D.nc + q] = 1;
     __syncthreads();
   } else if (D.nc > 0) {
-    const int32_t *clq = pl + D.off[28];
+    const int32_t *clq = pl + D.off[kSec_clq];
     const int nc = clq[0], c0 = clq[1];
     const int32_t *ct0 = clq + 2, *bend = clq + 2 + nc;
     // B0: border updates (columns p < c0) of every tail block and tail RHS
@@ -444,7 +448,7 @@ __global__ void __launch_bounds__(1024) sparse_llt_kernel(SparseDev D) {
   // LDS-operand FMAs and the W product as 7 readlane broadcasts (~2k cycles
   // per level at C3). Another summation order: x within fp64 round-off.
   if (!STAGE) {
-    const int32_t *lev_ptr = pl + D.off[4];
+    const int32_t *lev_ptr = pl + D.off[kSec_lev_ptr];
     const int a8 = lane >> 3, b8 = lane & 7;
     const bool act = a8 < 7 && b8 < 7;
     const int ac = a8 < 7 ? a8 : 6, bc = b8 < 7 ? b8 : 6;
@@ -478,7 +482,7 @@ __global__ void __launch_bounds__(1024) sparse_llt_kernel(SparseDev D) {
       __syncthreads();
     }
   } else {
-    const int32_t *lev_ptr = pl + D.off[4];
+    const int32_t *lev_ptr = pl + D.off[kSec_lev_ptr];
     for (int L = D.levels - 1; L >= 0; L--) {
       for (int c = lev_ptr[L] + wave; c < lev_ptr[L + 1]; c += NW) {
         const int k = lev_col[c];

@@ -72,8 +72,8 @@ __device__ void gcol_worker(const ColArgs &C, const GArgs &G) {
   __shared__ int sqw[kTailNW][kGMaxS];    // the sparse ancestors' positions q in struct(k), list order
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int32_t *pl = C.plan;
-  const int32_t *col_ptr = pl + C.off[1], *col_row = pl + C.off[2], *col_slot = pl + C.off[3],
-                *corder = pl + C.off[29];
+  const int32_t *col_ptr = pl + C.off[kSec_col_ptr], *col_row = pl + C.off[kSec_col_row],
+                *col_slot = pl + C.off[kSec_col_slot], *corder = pl + C.off[kSec_corder];
   const int want = C.epoch + 1, c0 = C.c0, nct = C.m - c0, nx = G.nx, nt = 7 * nct;
   const int nG = (int)gridDim.x - G.n_pairs;
   const int S = (nx + 63) / 64;

@@ -92,6 +92,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -165,20 +166,7 @@ int m3s_gn_solve(const m3s_gn_args *a, const double *edge_sums, void *stream) {
   return gn_solve_impl(a, edge_sums, nullptr, 0, S(stream));
 }
 
-int m3s_gn_release(const m3s_gn_args *a, void *stream) {
-  if (!a || !a->workspace) return M3S_EINVAL;
-  (void)stream;  // no sync: every queued upload reads pinned staging, not the entry
-  std::lock_guard<std::mutex> stage_lock(g_stage_mu);  // (lock order: staging, then registry)
-  std::lock_guard<std::mutex> g(g_reg_mu);
-  auto it = g_reg.find(a->workspace);
-  if (it == g_reg.end()) return M3S_OK;
-  if (it->second.host_pending && it->second.slot >= 0) {  // ids never read: free the slot (its
-    Staging *SG = stage_for_device();                      // event guards the reuse)
-    if (SG && it->second.slot < (int)SG->slots.size()) SG->slots[it->second.slot].busy = false;
-  }
-  g_reg.erase(it);
-  return M3S_OK;
-}
+int m3s_gn_release(const m3s_gn_args *a, void *) { return gn_release_impl(a); }
 
 size_t m3s_track_workspace_size(int64_t HW) {
   const int64_t chunks = chunks_for(HW, 1);
@@ -201,16 +189,9 @@ int64_t m3s_sparse_plan_debug(int32_t N, int64_t E, const int32_t *ri, const int
   build_sparse_plan(N, a, b, P, split, max_parts, dense_tail_min());
   PlanImage I;
   flatten_plan(P, I);
-  const int64_t offs[kPlanSections] = {
-      I.off_perm,     I.off_col_ptr,  I.off_col_row,     I.off_col_slot, I.off_lev_ptr,
-      I.off_lev_col,  I.off_dtr_ptr,  I.off_dtr_slot,    I.off_dtr_p,    I.off_task_lev_ptr,
-      I.off_task_dst, I.off_task_col, I.off_task_tr_ptr, I.off_tr_a,     I.off_tr_b,
-      I.off_asm_ptr,  I.off_asm_edge, I.off_g_ptr,       I.off_g_edge,   I.off_ctask_ptr,
-      I.off_items,    I.off_wave_ptr, I.off_witems,    I.off_part_q0,  I.off_part_q1,
-      I.off_part_tgt, I.off_dpart_ptr, I.off_opart_ptr, I.off_clq, I.off_corder, I.off_ctask0};
   if (meta) {
     meta[0] = P.m, meta[1] = P.S, meta[2] = P.levels;
-    for (int k = 0; k < kPlanSections; k++) meta[3 + k] = (int32_t)offs[k];
+    std::copy(I.off, I.off + kPlanSections, meta + 3);
     meta[3 + kPlanSections] = (int32_t)P.part_q0.size();
   }
   const int64_t n = (int64_t)I.data.size();

@@ -613,42 +613,14 @@ void build_sparse_plan(int N, const std::vector<int32_t> &ri, const std::vector<
 void flatten_plan(const SparsePlan &P, PlanImage &img) {
   img.data.clear();
   auto put = [&](const std::vector<int32_t> &v) {
-    const int64_t off = (int64_t)img.data.size();
+    const int off = (int)img.data.size();
     img.data.insert(img.data.end(), v.begin(), v.end());
     while (img.data.size() % 4) img.data.push_back(0);  // 16-B aligned sections
     return off;
   };
-  img.off_perm = put(P.perm);
-  img.off_col_ptr = put(P.col_ptr);
-  img.off_col_row = put(P.col_row);
-  img.off_col_slot = put(P.col_slot);
-  img.off_lev_ptr = put(P.lev_ptr);
-  img.off_lev_col = put(P.lev_col);
-  img.off_dtr_ptr = put(P.dtr_ptr);
-  img.off_dtr_slot = put(P.dtr_slot);
-  img.off_dtr_p = put(P.dtr_p);
-  img.off_task_lev_ptr = put(P.task_lev_ptr);
-  img.off_task_dst = put(P.task_dst);
-  img.off_task_col = put(P.task_col);
-  img.off_task_tr_ptr = put(P.task_tr_ptr);
-  img.off_tr_a = put(P.tr_a);
-  img.off_tr_b = put(P.tr_b);
-  img.off_asm_ptr = put(P.asm_ptr);
-  img.off_asm_edge = put(P.asm_edge);
-  img.off_g_ptr = put(P.g_ptr);
-  img.off_g_edge = put(P.g_edge);
-  img.off_ctask_ptr = put(P.ctask_ptr);
-  img.off_items = put(P.items);
-  img.off_wave_ptr = put(P.wave_ptr);
-  img.off_witems = put(P.witems);
-  img.off_part_q0 = put(P.part_q0);
-  img.off_part_q1 = put(P.part_q1);
-  img.off_part_tgt = put(P.part_tgt);
-  img.off_dpart_ptr = put(P.dpart_ptr);
-  img.off_opart_ptr = put(P.opart_ptr);
-  img.off_clq = put(P.clq);
-  img.off_corder = put(P.corder);
-  img.off_ctask0 = put(P.ctask0);
+#define M3S_X(name) img.off[kSec_##name] = put(P.name);
+  M3S_PLAN_SECTIONS(M3S_X)
+#undef M3S_X
 }
 
 }  // namespace m3s

@@ -7,6 +7,8 @@
 // the elimination tree so the numeric phase (m3s_gn.hip, sparse_llt_kernel)
 // can factor independent columns concurrently. Computed once per solve call
 // (the edge structure is fixed across its GN iterations).
+// The order of the plan's sections in its flattened image is declared once,
+// here: M3S_PLAN_SECTIONS, below.
 #pragma once
 #include <stdint.h>
 
@@ -79,16 +81,29 @@ void build_sparse_plan(int N, const std::vector<int32_t> &ri, const std::vector<
                        bool schedule = true);
 void schedule_plan_items(SparsePlan &P);
 
-// Flattened int32 image of the plan (offsets of each array into it).
+// The sections of the flattened plan image, in image order: one row per
+// SparsePlan array. This list is the one declaration of that order: the ids
+// (kSec_<name>, ending in kPlanSections), the names, flatten_plan and every
+// reader of PlanImage::off (host and kernels) derive from it. The Python side
+// restates it as PLAN_SECTIONS (mast3r_slam_backends/gn.py), and
+// tests/test_sparse_plan.py holds the two equal.
+#define M3S_PLAN_SECTIONS(X)                                                                        \
+  X(perm) X(col_ptr) X(col_row) X(col_slot) X(lev_ptr) X(lev_col) X(dtr_ptr) X(dtr_slot) X(dtr_p)  \
+  X(task_lev_ptr) X(task_dst) X(task_col) X(task_tr_ptr) X(tr_a) X(tr_b) X(asm_ptr) X(asm_edge)    \
+  X(g_ptr) X(g_edge) X(ctask_ptr) X(items) X(wave_ptr) X(witems) X(part_q0) X(part_q1) X(part_tgt) \
+  X(dpart_ptr) X(opart_ptr) X(clq) X(corder) X(ctask0)
+#define M3S_X(name) kSec_##name,
+enum PlanSection : int { M3S_PLAN_SECTIONS(M3S_X) kPlanSections };
+#undef M3S_X
+#define M3S_X(name) #name,
+constexpr const char *kPlanSectionNames[kPlanSections] = {M3S_PLAN_SECTIONS(M3S_X)};
+#undef M3S_X
+
+// Flattened int32 image of the plan: off[s] is where section s starts in data.
 struct PlanImage {
   std::vector<int32_t> data;
-  int64_t off_perm, off_col_ptr, off_col_row, off_col_slot, off_lev_ptr, off_lev_col, off_dtr_ptr,
-      off_dtr_slot, off_dtr_p, off_task_lev_ptr, off_task_dst, off_task_col, off_task_tr_ptr,
-      off_tr_a, off_tr_b, off_asm_ptr, off_asm_edge, off_g_ptr, off_g_edge, off_ctask_ptr,
-      off_items, off_wave_ptr, off_witems, off_part_q0, off_part_q1, off_part_tgt, off_dpart_ptr,
-      off_opart_ptr, off_clq, off_corder, off_ctask0;
+  int off[kPlanSections];
 };
-constexpr int kPlanSections = 31;
 constexpr int kLltWaves = 16;  // waves of sparse_llt_kernel (1024 threads)
 void flatten_plan(const SparsePlan &P, PlanImage &img);
 

@@ -84,6 +84,7 @@ def version() -> str:
     return _sym("m3s_version")().decode()
 
 
+# the rows of M3S_PLAN_SECTIONS (csrc/m3s_symbolic.h), in order (tests/test_sparse_plan.py)
 PLAN_SECTIONS = ("perm", "col_ptr", "col_row", "col_slot", "lev_ptr", "lev_col", "dtr_ptr",
                  "dtr_slot", "dtr_p", "task_lev_ptr", "task_dst", "task_col", "task_tr_ptr", "tr_a",
                  "tr_b", "asm_ptr", "asm_edge", "g_ptr", "g_edge", "ctask_ptr", "items", "wave_ptr", "witems",

@@ -163,3 +163,49 @@ def test_stepwise_edge_sums_fused_reduce_across_ranges(be):
     # the sub-range's sums are the same edges' sums (other chunking: fp32
     # partials grouped differently)
     np.testing.assert_allclose(S1, A1[eb:ee], rtol=1e-4, atol=1e-6 * np.abs(A1).max())
+
+
+def test_stepwise_host_prepare_cache_hit_starts_from_fresh_call_state(be, knobs):
+    """A plan-cache entry is a plan, not the call that built it. Host prepare
+    (knob prologue = 0), 48x64: 3 chunks per edge, not a power of two. Call 1
+    caches its plan at its first solve, after a linearize with edge sums has
+    counted arrivals; call 2 on a fresh workspace hits the cache at prepare and
+    must count its arrivals from its own zeroed counters: its edge sums are
+    finite and bitwise those of call 1. With an arrival count inherited from
+    the cached call, the wrong chunk of an edge would write the edge's sums
+    (the second arrival of three; it reads the third chunk's partial, which
+    is usually stored by then, so that fault shows only when timing allows).
+    The same with the cache off for call 2 (a miss: the plan is deferred)."""
+    from mast3r_slam_amd import synthetic
+    from mast3r_slam_amd.distributed import HipOps
+
+    knobs("prologue", 0)
+    g = synthetic.make_graph(7, 48, 64, seed=41)
+    sig = dict(sigma_a=0.003, sigma_b=10.0, C_thresh=0.0, Q_thresh=1.5)
+    Xs = g.Xs.to(DEV).contiguous()
+    E = g.n_edges
+
+    def call(solve):
+        Twc = g.T_init.data.clone().to(DEV).contiguous()
+        ops = HipOps(be.MODE_RAYS, Twc, Xs, g.Cs.to(DEV).contiguous(), g.ii.to(DEV), g.jj.to(DEV),
+                     g.idx_ii2jj.to(DEV).contiguous(), g.valid_match.to(DEV).contiguous(),
+                     g.Q.to(DEV).contiguous(), E, None, **sig)
+        ops.ws.zero_()
+        ops.prepare(0.0)
+        es = torch.full((E, ops.stride), float("nan"), dtype=torch.float64, device=DEV)
+        ops.linearize(0, E, es)
+        if solve:
+            ops.solve(es)
+        torch.cuda.synchronize()
+        ops.close()
+        return es.cpu().numpy()
+
+    for cache2 in (1, 0):
+        # a plan-shaping knob set to another value drops the plan cache: call 1 starts cold
+        be.set_knob("dense_tail_min", be.set_knob("dense_tail_min", 1 << 20))
+        knobs("plan_cache", 1)
+        es1 = call(True)
+        knobs("plan_cache", cache2)
+        es2 = call(False)
+        assert np.isfinite(es1).all() and np.isfinite(es2).all()
+        np.testing.assert_array_equal(es2, es1)

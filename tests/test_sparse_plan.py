@@ -237,3 +237,28 @@ def test_plan_fill_is_sparse_on_loop_graph(be):
     dense_slots = 31 * 32 // 2
     assert p["S"] < 0.4 * dense_slots
     assert p["levels"] < 31
+
+
+def test_plan_sections_are_declared_once(be):
+    """The row list of csrc/m3s_symbolic.h (M3S_PLAN_SECTIONS: the ids the
+    kernels index PlanImage::off with, and what flatten_plan writes) is
+    be.PLAN_SECTIONS, name for name and in order, and sparse_plan's table of
+    section lengths names sections only."""
+    import ast
+    import inspect
+    import os
+    import re
+    import textwrap
+
+    path = os.path.join(os.path.dirname(__file__), "..", "mast3r-slam-ysh_amd", "csrc", "m3s_symbolic.h")
+    text = open(path).read().replace("\\\n", " ")
+    (rows,) = re.findall(r"^#define M3S_PLAN_SECTIONS\(X\)(.*)$", text, re.M)
+    names = re.findall(r"X\((\w+)\)", rows)
+    assert re.sub(r"X\(\w+\)|\s", "", rows) == ""  # nothing but rows in the list
+    assert tuple(names) == be.PLAN_SECTIONS
+    assert len(set(names)) == len(names) == 31
+    tree = ast.parse(textwrap.dedent(inspect.getsource(be.sparse_plan)))
+    lens = [n.value for n in ast.walk(tree)
+            if isinstance(n, ast.Assign) and getattr(n.targets[0], "id", None) == "lens"]
+    assert len(lens) == 1 and lens[0].keys
+    assert {k.value for k in lens[0].keys} <= set(be.PLAN_SECTIONS)
