@@ -253,6 +253,13 @@ int64_t m3s_sparse_plan_debug(int32_t N, int64_t E, const int32_t *ri, const int
  * order flags, rank_i, rank_j, first, partials, edge_sums, A, fin, plan, Lblk,
  * Dinv, tail, tasks, planes, total (offs[15]). Returns the total. */
 size_t m3s_gn_layout_debug(int64_t N, int64_t HW, int64_t E, size_t *offs);
+/* Diagnostic, host only (no device is touched): the name of the launch path
+ * the solver takes for N poses, HW pixels and E edges with ranks (ri, rj)
+ * under the current knobs, as the plan records it: "dense", "lds_plan",
+ * "lds", "chip", "global_split", "global" ("pending" for N = 1: nothing to
+ * solve). A static string; NULL for bad arguments (N < 1, HW < 1, E < 0, a
+ * missing array, a rank outside [0, N)). */
+const char *m3s_gn_plan_path_debug(int64_t N, int64_t HW, int64_t E, const int32_t *ri, const int32_t *rj);
 /* instrumented builds only: which = 0 persistent-tracker phase stamps
  * [2][16][8] (-DM3S_TRK_STAMPS), 1 column-task stamps [4][2048][4]
  * (-DM3S_COL_STAMPS); wall-clock ticks. 1 if present, 0 otherwise

@@ -1,7 +1,9 @@
 // gn/launch.h — part of the m3s_gn.hip translation unit (not a stand-alone header).
-// The linearize launches of the host: the in-call timing event slots,
-// launch_lin, launch_linearize, dispatch_linearize (the first host mention of
-// the linearize kernel templates), vec_ok and read_K.
+// The linearize launches of the host: the in-call timing event slots and
+// launch_timed (the one launch that takes an armed event pair; gn/solve.h
+// uses it for sparse_llt_kernel<1>), launch_lin, launch_linearize,
+// dispatch_linearize (the first host mention of the linearize kernel
+// templates), vec_ok and read_K.
 // Relies on the linearize and gathering kernels (gn/linearize.h,
 // gn/gather.h), launch_ok (gn/args.h) and gn/knobs.h (gather_lds_path).
 
@@ -11,22 +13,27 @@
 // timestamps (the kernel's span, as a kernel trace records it; events
 // recorded around the launch read 8-12% more, profiles/r04/prof_split_*.txt)
 // {start, stop}; thread_local: set and consumed by one gn_full call on its own
-// thread (a call on another thread without timing never sees it). launch_lin
-// clears it when it used the pair, so the caller can tell a span whose
-// linearize went through another launch (the pack == 0 path) and fall back to
-// the events recorded around it.
+// thread (a call on another thread without timing never sees it).
+// launch_timed clears it when it used the pair, so the caller can tell a span
+// whose linearize went through another launch (the pack == 0 path) and fall
+// back to the events recorded around it.
 thread_local hipEvent_t *g_lin_ext_ev = nullptr;
-// the same for the one-workgroup solve's launch (sparse_llt_kernel, small
+// the same for the one-workgroup solve's launch (sparse_llt_kernel<1>, small
 // graphs: the whole solve of an iteration is that one dispatch)
 thread_local hipEvent_t *g_slv_ext_ev = nullptr;
+// One launch that takes the armed pair `ev` (and clears it), or a plain one.
+template <typename K, typename A>
+void launch_timed(hipEvent_t *&ev, K kernel, dim3 g, dim3 b, size_t lds, hipStream_t st, const A &args) {
+  if (ev) {
+    hipExtLaunchKernelGGL(kernel, g, b, lds, st, ev[0], ev[1], 0, args);
+    ev = nullptr;
+  } else {
+    kernel<<<g, b, lds, st>>>(args);
+  }
+}
 template <typename K>
 void launch_lin(K kernel, dim3 g, dim3 b, hipStream_t st, const LinArgs &L) {
-  if (g_lin_ext_ev) {
-    hipExtLaunchKernelGGL(kernel, g, b, 0, st, g_lin_ext_ev[0], g_lin_ext_ev[1], 0, L);
-    g_lin_ext_ev = nullptr;
-  } else {
-    kernel<<<g, b, 0, st>>>(L);
-  }
+  launch_timed(g_lin_ext_ev, kernel, g, b, 0, st, L);
 }
 
 // pack: 0 gathering kernel, 1 gathering kernel that stores the planes,

@@ -1,19 +1,43 @@
 // gn/plan.h — part of the m3s_gn.hip translation unit (not a stand-alone header).
-// From edge ids to a plan on the device: PlanRecord (the one declaration of
-// what a solve launch reads of a plan), PlanMeta and the workspace registry,
+// From edge ids to a plan on the device: SolvePath (the row list of the
+// launch paths), PlanRecord (the one declaration of what a solve launch reads
+// of a plan, its path included), PlanMeta and the workspace registry,
 // pinned staging, the plan cache (find_cached_plan), set_knob,
-// build_plan_meta, build_eorder, upload_plan, adopt_plan, gn_prepare_impl
+// build_plan_meta (the one place that decides a plan's path: the LDS budget,
+// the chip-wide condition and the shaping knobs), build_eorder, upload_plan,
+// adopt_plan, gn_prepare_impl
 // (host prepare), finish_plan / host_finish, gn_prepare_async (the prologue
 // launch) and gn_release_impl.
 // Relies on gn/layout.h (Layout / gn_layout), gn/llt_blocks.h
 // (kStageDoubles, kSplitUpdates), gn/prologue.h (the call prologue), gn/args.h
 // (S, launch_ok) and gn/knobs.h; declares set_lds_attributes_once, which
-// gn/iterate.h defines.
+// gn/solve.h defines.
+
+// The launches that solve a plan (gn/solve.h has one launch function per
+// path). One row per path: the enum and the names (m3s_gn_plan_path_debug)
+// are derived from the list. build_plan_meta decides the path, once, from the
+// plan and the shaping knobs; nothing re-derives it at launch.
+#define M3S_SOLVE_PATHS(X)                                                                                \
+  X(pending)      /* no plan yet (a record whose plan is still to be built): nothing may launch */       \
+  X(dense)        /* no sparse plan that fits: the tiled (test build: register) dense Cholesky */        \
+  X(lds_plan)     /* sparse_llt_kernel<1>: factor and plan in the LDS */                                 \
+  X(lds)          /* sparse_llt_kernel<2>: factor in the LDS */                                          \
+  X(chip)         /* df_factor_kernel -> dense tail -> back-substitution, over the chip */               \
+  X(global_split) /* sparse_llt_kernel<0> in two phases around border_kernel (+ tail_llt_kernel) */      \
+  X(global)       /* sparse_llt_kernel<0> alone */
+#define M3S_PATH_ID(name) name,
+#define M3S_PATH_NAME(name) #name,
+enum class SolvePath : int { M3S_SOLVE_PATHS(M3S_PATH_ID) };
+constexpr const char *kSolvePathNames[] = {M3S_SOLVE_PATHS(M3S_PATH_NAME)};
+#undef M3S_PATH_ID
+#undef M3S_PATH_NAME
 
 // What a solve launch reads of a plan. Built once per edge set
 // (build_plan_meta), kept by the plan cache and copied whole: a field added
 // here reaches the cold, the cached and the host-prepare path alike.
 struct PlanRecord {
+  SolvePath path = SolvePath::pending;
+  bool mfma_tail = false;  // global_split: the dense tail fits tail_llt_kernel (else phase 2 factors it)
   bool sparse = false;
   int store = 0;  // sparse_llt_kernel<STORE>
   bool asm_lds = false;  // LDS factor with room for the staged fin blocks: assembly in the LLT kernel
@@ -148,9 +172,9 @@ void build_eorder(const std::vector<int32_t> &rj, int64_t eb, int64_t E_loc, std
 }
 
 constexpr size_t kMaxLdsBytes = 150 * 1024;
-// Defined behind gn_solve_impl: its body names the sparse_llt_kernel
-// specialisations, and where a kernel template is first named decides its
-// place in the device code (the order rule, m3s_gn.hip).
+// Defined behind the launch functions of gn/solve.h: its body names the
+// sparse_llt_kernel specialisations, and where a kernel template is first
+// named decides its place in the device code (the order rule, m3s_gn.hip).
 void set_lds_attributes_once();
 
 // Host symbolic plans of recent edge sets (the same factor graph is usually
@@ -217,7 +241,11 @@ PlanMeta build_plan_meta(const m3s_gn_args *a, const Layout &Ly, const std::vect
     // substitution) needs neither: at 256 KFs that halves the host analysis.
     build_sparse_plan((int)a->N, ri, rj, P, 0, 0, dense_tail_min(), false);
     const bool global_factor = sizeof(double) * ((size_t)(P.S + P.m) * 49 + (size_t)P.m * 7) > kMaxLdsBytes;
-    const bool chip_path = global_factor && cols_path() && P.m <= 512 && (P.nc == 0 || 7 * P.nc + 1 <= 16 * kTailMaxT);
+    // the chip-wide launches take a factor in global memory of up to 512
+    // columns whose dense tail (if any) fits tail_llt_kernel's tiles
+    const bool tail_fits = 7 * P.nc + 1 <= 16 * kTailMaxT;
+    const bool chip_ok = cols_path() && P.m <= 512 && (P.nc == 0 || tail_fits);
+    const bool chip_path = global_factor && chip_ok;
     if (global_factor && !chip_path)  // split long update lists for the staged global-factor products
       build_sparse_plan((int)a->N, ri, rj, P, kSplitUpdates, Ly.slot_cap - 1, dense_tail_min(), true);
     else if (!chip_path)
@@ -273,7 +301,18 @@ PlanMeta build_plan_meta(const m3s_gn_args *a, const Layout &Ly, const std::vect
       }
       std::copy(img.off, img.off + kPlanSections, R.off);
       built.h_plan = std::move(img.data);
+      // the launches of this plan: the LDS kernels by what fits beside the
+      // factor, else (a factor in global memory) over the chip, else on one
+      // workgroup, split around the tail border when there is a dense tail
+      if (R.store != 0)
+        R.path = R.store == 1 ? SolvePath::lds_plan : SolvePath::lds;
+      else if (chip_ok)
+        R.path = SolvePath::chip;
+      else
+        R.path = P.nc > 0 && border_split() ? SolvePath::global_split : SolvePath::global;
+      R.mfma_tail = tail_fits && tail_mfma();
     }
+    if (!R.sparse) R.path = SolvePath::dense;
   }
   (void)E;
   return built;
@@ -346,6 +385,7 @@ int adopt_plan(Staging *SG, PlanMeta &M, const PlanRecord &plan, std::vector<int
   M.plan = plan;
   M.h_plan = std::move(image);
   M.plan_pending = false;
+  if (plan.sparse && plan.lds_bytes > 64 * 1024) set_lds_attributes_once();
   bool ok = reset_plan_flags(M.plan, Ly, ws, st);
   apply_drop_item(M);
   ok &= upload_plan(SG, M, at<char>(ws, Ly.plan), st);
@@ -386,6 +426,7 @@ int gn_prepare_impl(const m3s_gn_args *a, hipStream_t st) {
     // outcome until then (the dense path reads partials either way)
     meta.plan.sparse = !bad && !force_dense && a->N > 1;
     meta.plan_pending = !bad && a->N > 1;
+    if (bad) meta.plan.path = SolvePath::dense;  // a stopped call: the dense launches return at the stop flag
   }
   meta.force_dense = force_dense;
   // ranks and the full range's edge order now (the first linearize needs them)
@@ -448,7 +489,6 @@ int finish_plan(const m3s_gn_args *a, const Layout &Ly, hipStream_t st) {
     force_dense = it->second.force_dense;
   }
   PlanMeta built = build_plan_meta(a, Ly, ri, rj, force_dense);
-  if (built.plan.sparse && built.plan.lds_bytes > 64 * 1024) set_lds_attributes_once();
   std::lock_guard<std::mutex> stage_lock(g_stage_mu);
   Staging *SG = stage_for_device();
   if (!SG) return M3S_ELAUNCH;
@@ -510,7 +550,6 @@ int host_finish(const m3s_gn_args *a, hipStream_t st) {
   PlanRecord plan;
   std::vector<int32_t> image;
   const bool hit = !bad && find_cached_plan(a, force_dense, ri, rj, plan, image);
-  if (hit && plan.sparse && plan.lds_bytes > 64 * 1024) set_lds_attributes_once();
   std::lock_guard<std::mutex> stage_lock(g_stage_mu);
   Staging *SG = stage_for_device();
   if (!SG) return M3S_ELAUNCH;
@@ -519,7 +558,7 @@ int host_finish(const m3s_gn_args *a, hipStream_t st) {
   M.host_pending = false, M.slot = -1;
   M.h_ri = std::move(ri), M.rj = std::move(rj);
   if (bad) {
-    M.plan.sparse = false, M.plan_pending = false;
+    M.plan.sparse = false, M.plan.path = SolvePath::dense, M.plan_pending = false;
     return M3S_OK;
   }
   if (!hit) return M3S_OK;  // plan_pending: finish_plan builds it

@@ -9,7 +9,8 @@
 // gn/chol_tiled.h, gn/llt_blocks.h, gn/sparse_llt.h, gn/col_tasks.h,
 // gn/dataflow.h, gn/tail_llt.h, gn/tail_cyc.h, gn/tail_pair.h,
 // gn/chol_small.h, gn/prologue.h, gn/border.h), then the host side of the
-// backend (gn/args.h, gn/knobs.h, gn/launch.h, gn/plan.h, gn/iterate.h), the
+// backend (gn/args.h, gn/knobs.h, gn/launch.h, gn/plan.h, gn/iterate.h,
+// gn/solve.h: the launch functions of the solve, one per path of a plan), the
 // tracker (gn/track.h) and the track_frame front end (gn/track_frame.h), then
 // the two debug kernels (gn/debug.h). The gn/*.h files are parts of this file,
 // not stand-alone headers: each is text inside the one anonymous namespace
@@ -31,13 +32,17 @@
 //                                  linearize_kernel (gn/linearize.h) where the
 //                                  gathering kernel does not apply
 //                later iterations  linearize_packed_kernel (gn/linearize.h)
-//              then the solve (gn_solve_impl, gn/iterate.h), by the plan:
-//                factor fits the LDS (small graphs): sparse_llt_kernel<1> / <2>
+//              then the solve (gn_solve_impl, gn/solve.h), by the path that
+//              build_plan_meta (gn/plan.h) wrote into the plan (SolvePath), one
+//              launch function per path:
+//                factor fits the LDS (small graphs; lds_plan / lds, solve_lds):
+//                  sparse_llt_kernel<1> / <2>
 //                  (gn/sparse_llt.h), one workgroup: assembly, LLT,
 //                  back-substitution, retraction, stop flag;
 //                  assemble_slots_kernel (gn/llt_blocks.h) first when the
 //                  staged edge blocks do not fit beside the factor
-//                else, up to 512 columns (large graphs), over the chip:
+//                else, up to 512 columns (large graphs), over the chip (chip,
+//                  solve_chip):
 //                  assemble_slots_kernel,
 //                  df_factor_kernel (gn/dataflow.h, the wave-level dataflow
 //                  factorisation),
@@ -45,10 +50,12 @@
 //                  tail (from 32 tail columns its extra workgroups run the
 //                  sparse back-substitution, gcol_worker, gn/tail_pair.h),
 //                  else col_backsub_kernel (gn/dataflow.h)
-//                else: sparse_llt_kernel<0>, in two phases around border_kernel
-//                  (gn/border.h) and tail_llt_kernel (gn/tail_llt.h, the dense
-//                  tail on the f64 MFMA) with a dense tail
-//                no sparse plan that fits: edge_reduce_kernel (gn/gather.h),
+//                else (global_split / global, solve_global): sparse_llt_kernel<0>,
+//                  in two phases around border_kernel (gn/border.h) and
+//                  tail_llt_kernel (gn/tail_llt.h, the dense tail on the f64
+//                  MFMA) with a dense tail
+//                no sparse plan that fits (dense, solve_dense):
+//                  edge_reduce_kernel (gn/gather.h),
 //                  assemble_kernel (gn/assemble.h) and the tiled dense Cholesky:
 //                  potrf_tile_kernel (gn/chol_tiled.h), trsm_tile_kernel
 //                  (gn/chol_tiled.h), update_tiles_kernel (gn/chol_tiled.h),
@@ -74,8 +81,11 @@
 // Order rule: the include list is the order of the device code. The parts keep
 // their places in the list, device functions and kernels keep their relative
 // order inside a part, and the first host mention of each kernel template
-// stays where it is (gn/launch.h, gn/plan.h, gn/iterate.h; it decides where
-// the instantiation lands). The code object holds real calls to
+// stays where it is (gn/launch.h, gn/plan.h, gn/iterate.h, gn/solve.h; it
+// decides where the instantiation lands: gn/solve.h stands behind
+// gn/iterate.h because the linearize templates come first, and its launch
+// functions stand in the order chip, lds, global, dense, then
+// set_lds_attributes_once). The code object holds real calls to
 // non-inlined device functions, so a reordering changes pc-relative literals
 // and the device code can no longer be compared instruction for instruction
 // with the build before (tools/code_identity.py). Host code may move otherwise.
@@ -128,6 +138,7 @@ namespace {
 #include "gn/launch.h"
 #include "gn/plan.h"
 #include "gn/iterate.h"
+#include "gn/solve.h"
 #include "gn/track.h"
 #include "gn/track_frame.h"
 #include "gn/debug.h"
@@ -287,6 +298,17 @@ int m3s_debug_sim3(int op, const float *a, const float *b, float *out, int64_t n
   if (n == 0) return M3S_OK;
   sim3_debug_kernel<<<(unsigned)((n + 255) / 256), 256, 0, S(stream)>>>(op, a, b, out, n);
   return hipGetLastError() == hipSuccess ? M3S_OK : M3S_ELAUNCH;
+}
+
+const char *m3s_gn_plan_path_debug(int64_t N, int64_t HW, int64_t E, const int32_t *ri, const int32_t *rj) {
+  if (N < 1 || HW < 1 || E < 0 || (E > 0 && (!ri || !rj))) return nullptr;
+  for (int64_t e = 0; e < E; e++)
+    if (ri[e] < 0 || ri[e] >= N || rj[e] < 0 || rj[e] >= N) return nullptr;
+  m3s_gn_args a{};
+  a.N = N, a.HW = HW, a.E = E;
+  const PlanMeta built = build_plan_meta(&a, gn_layout(N, HW, E), std::vector<int32_t>(ri, ri + E),
+                                         std::vector<int32_t>(rj, rj + E), force_dense_knob());
+  return kSolvePathNames[(int)built.plan.path];
 }
 
 size_t m3s_gn_layout_debug(int64_t N, int64_t HW, int64_t E, size_t *offs) {

@@ -71,6 +71,7 @@ _SIGNATURES = {
     "m3s_version": (ctypes.c_char_p, []),
     "m3s_sparse_plan_debug": (_I64, [_I32, _I64, _VP, _VP, _I32, _I32, _VP, _I64, _VP]),
     "m3s_gn_layout_debug": (_SIZE, [_I64, _I64, _I64, _VP]),
+    "m3s_gn_plan_path_debug": (ctypes.c_char_p, [_I64, _I64, _I64, _VP, _VP]),
     "m3s_debug_stamps": (_INT, [_INT, _VP]),
     "m3s_debug_sim3": (_INT, [_INT, _VP, _VP, _VP, _I64, _VP]),
     "m3s_debug_copy": (_INT, [_VP, _VP, _I64, _INT, _VP]),
@@ -176,6 +177,22 @@ def debug_copy(src: torch.Tensor, dst: torch.Tensor, blocks: int = 4096):
 def workspace_layout(N, HW, E):
     """Byte offsets of the GN workspace sections (diagnostics/tests)."""
     return _layout("m3s_gn_layout_debug", LAYOUT_SECTIONS, N, HW, E)
+
+
+def plan_path(N, HW, ri, rj) -> str:
+    """The launch path the solver takes for N poses, HW pixels and the edge
+    ranks (ri, rj) under the current knobs (m3s_gn_plan_path_debug; CPU only):
+    "dense", "lds_plan", "lds", "chip", "global_split" or "global"."""
+    import numpy as np
+
+    ri = np.ascontiguousarray(ri, dtype=np.int32)
+    rj = np.ascontiguousarray(rj, dtype=np.int32)
+    name = None
+    if ri.size == rj.size:
+        name = _sym("m3s_gn_plan_path_debug")(int(N), int(HW), ri.size, _VP(ri.ctypes.data), _VP(rj.ctypes.data))
+    if name is None:
+        raise RuntimeError("plan_path: bad arguments")
+    return name.decode()
 
 
 def sparse_plan(N, ri, rj, split=0, max_parts=0):

@@ -70,6 +70,14 @@ def constrained(g):
     return torch.from_numpy(np.stack([constrain_points_to_ray((g.H, g.W), x, K) for x in g.Xs.numpy()]))
 
 
+def path_of(be, g):
+    """The solve path of graph g under the current knobs, on the library in
+    use (be.plan_path: the plan's own record of its launches; host only)."""
+    ids = np.concatenate([g.ii.cpu().numpy(), g.jj.cpu().numpy()])
+    ri, rj = np.unique(ids, return_inverse=True)[1].reshape(2, -1)
+    return be.plan_path(g.Xs.shape[0], g.Xs.shape[1], ri, rj)
+
+
 @pytest.fixture(scope="module")
 def graph_small():
     from mast3r_slam_amd import synthetic
@@ -254,6 +262,7 @@ def test_gn_broken_plan_times_out_as_solve_failure(test_lib, be, knobs, N, tail)
     if tail is not None:
         knobs("dense_tail_min", tail)
     knobs("debug_drop_item", "0")
+    assert path_of(be, g) == ("lds_plan" if N == 12 else "chip")
     t0 = time.time()
     T_gpu, dx, info = run_gpu(be, "rays", g, 1, 0.0)
     dt = time.time() - t0
@@ -288,6 +297,7 @@ def test_workspace_reuse_across_solver_paths(be, knobs):
 
     nbytes = max(be._lib.m3s_gn_workspace_size(g.Xs.shape[0], g.Xs.shape[1], g.n_edges) for g in (big, small))
     ws = torch.zeros(nbytes, dtype=torch.uint8, device=DEV)
+    assert [path_of(be, g) for g in (big, small, big)] == ["chip", "lds_plan", "chip"]
     seq = [call(g, ws) for g in (big, small, big)]
     for g, got in zip((big, small, big), seq):
         ref = call(g, None)
@@ -424,6 +434,7 @@ def test_gn_over_capacity_plan_takes_dense_fallback(be):
     g = synthetic.make_graph(N, 8, 12, seed=45, edges=(ii_u, jj_u))
     m = N - 1
     assert m * (m + 1) // 2 > 64 * m + 4096 + 1
+    assert path_of(be, g) == "dense"
     # step 1 from the initial poses
     T1_gpu, dx1_gpu, info1 = run_gpu(be, "rays", g, 1, 0.0)
     _, dx1_ref, _, failed = run_oracle("rays", g, 1, 0.0)
@@ -483,18 +494,28 @@ def test_gn_singular_global_factor_zero_dx(be):
     np.testing.assert_array_equal(T_gpu, g.T_init.data.numpy())
 
 
-@pytest.mark.parametrize("N,tail", [(6, "8"), (32, "8"), (70, "8"), (32, "3"), (70, "0"), (140, "8"), (256, "24")])
-def test_sparse_llt_matches_dense_llt(test_lib, be, N, tail, knobs):
-    """Block-sparse LLT (default; LDS-resident for small plans, global for
-    N >= 70; the top clique as a dense right-looking tail when it has at least
-    M3S_DENSE_TAIL_MIN columns, 0 = never) against the dense fallback
-    (M3S_DENSE=1) on identical inputs."""
+_LLT_CASES = [(6, "8", 1, "lds_plan"), (32, "8", 1, "lds_plan"), (70, "8", 1, "chip"), (32, "3", 1, "lds_plan"),
+              (70, "0", 1, "chip"), (140, "8", 1, "chip"), (256, "24", 1, "chip"), (140, "8", 0, "global_split")]
+
+
+@pytest.mark.parametrize("N,tail,cols,path", _LLT_CASES,
+                         ids=[f"{N}-{tail}" + ("" if cols else "-cols0") for N, tail, cols, _ in _LLT_CASES])
+def test_sparse_llt_matches_dense_llt(test_lib, be, N, tail, cols, path, knobs):
+    """Block-sparse LLT (default; LDS-resident for small plans, over the chip
+    from N = 70; the top clique as a dense right-looking tail when it has at
+    least M3S_DENSE_TAIL_MIN columns, 0 = never) against the dense fallback
+    (M3S_DENSE=1) on identical inputs. cols = 0: the large graph on the
+    one-workgroup kernel in two phases around border_kernel and
+    tail_llt_kernel, the launches the product takes above 512 columns."""
     from mast3r_slam_amd import synthetic
 
     knobs("dense_tail_min", tail)
+    knobs("cols", cols)
     g = synthetic.make_graph(N, 24, 32, seed=90 + N)
+    assert path_of(be, g) == path
     T_s, dx_s, info_s = run_gpu(be, "rays", g, 3, 0.0)
     knobs("dense", "1")
+    assert path_of(be, g) == "dense"
     T_d, dx_d, info_d = run_gpu(be, "rays", g, 3, 0.0)
     knobs("dense", 0)
     assert info_s[be.INFO_ITERS] == info_d[be.INFO_ITERS] == 3
@@ -503,17 +524,22 @@ def test_sparse_llt_matches_dense_llt(test_lib, be, N, tail, knobs):
 
 
 def test_mfma_tail_matches_block_tail_and_is_deterministic(test_lib, be, knobs):
-    """Global factor with a dense tail: tail_llt_kernel (the top clique on the
-    f64 MFMA, 16x16 tiles, the default) against the 7x7-block tail of
-    sparse_llt_kernel (M3S_TAIL_MFMA=0) on identical inputs; the MFMA path is
-    bitwise reproducible run to run (the sharded ranks rely on it)."""
+    """Global factor with a dense tail on the one-workgroup kernel (cols = 0:
+    the launches the product takes above 512 columns, where M3S_TAIL_MFMA is
+    read): tail_llt_kernel (the top clique on the f64 MFMA, 16x16 tiles, the
+    default) against the 7x7-block tail of sparse_llt_kernel (M3S_TAIL_MFMA=0)
+    on identical inputs; the MFMA path is bitwise reproducible run to run (the
+    sharded ranks rely on it)."""
     from mast3r_slam_amd import synthetic
 
     knobs("dense_tail_min", "8")
+    knobs("cols", 0)
     g = synthetic.make_graph(140, 24, 32, seed=77)
+    assert path_of(be, g) == "global_split"
     T_a, dx_a, info_a = run_gpu(be, "rays", g, 3, 0.0)
     T_a2, dx_a2, _ = run_gpu(be, "rays", g, 3, 0.0)
     knobs("tail_mfma", "0")
+    assert path_of(be, g) == "global_split"  # the same launches but tail_llt_kernel
     T_b, dx_b, info_b = run_gpu(be, "rays", g, 3, 0.0)
     assert info_a[be.INFO_ITERS] == info_b[be.INFO_ITERS] == 3
     assert info_a[be.INFO_SOLVE_FAIL] == info_b[be.INFO_SOLVE_FAIL] == 0
@@ -554,6 +580,7 @@ def test_block_dataflow_matches_column_tasks_bitwise(test_lib, be, N, knobs):
     from mast3r_slam_amd import synthetic
 
     g = synthetic.make_graph(N, 12, 16, seed=700 + N)
+    assert path_of(be, g) == "chip"
     T_a, dx_a, info_a = run_gpu(be, "rays", g, 3, 0.0)
     knobs("df", "0")
     T_b, dx_b, info_b = run_gpu(be, "rays", g, 3, 0.0)
@@ -573,6 +600,7 @@ def test_tail_pairs_match_tail_columns_bitwise(test_lib, be, N, knobs):
 
     g = synthetic.make_graph(N, 12, 16, seed=850 + N)
     knobs("gcomb", "0")  # both with col_backsub_kernel (tail_cyc_kernel has no workers)
+    assert path_of(be, g) == "chip"
     T_a, dx_a, info_a = run_gpu(be, "rays", g, 3, 0.0)
     knobs("tail_pair", "0")
     T_b, dx_b, info_b = run_gpu(be, "rays", g, 3, 0.0)
@@ -592,6 +620,7 @@ def test_tail_over_workgroups_matches_one_workgroup(test_lib, be, N, knobs):
     from mast3r_slam_amd import synthetic
 
     g = synthetic.make_graph(N, 12, 16, seed=800 + N)
+    assert path_of(be, g) == "chip"
     T_a, dx_a, info_a = run_gpu(be, "rays", g, 3, 0.0)
     knobs("tail_cyc", "0")
     T_b, dx_b, info_b = run_gpu(be, "rays", g, 3, 0.0)
@@ -692,6 +721,7 @@ def test_sparse_backsub_workers_match_column_tasks(test_lib, be, N, knobs):
 
     g = synthetic.make_graph(N, 12, 16, seed=880 + N)
     knobs("gcomb_min_nc", "0")  # the workers on every tail size (the product takes them from 32 columns)
+    assert path_of(be, g) == "chip"
     T_a, dx_a, info_a = run_gpu(be, "rays", g, 3, 0.0)
     knobs("gcomb", "0")
     T_b, dx_b, info_b = run_gpu(be, "rays", g, 3, 0.0)

@@ -262,3 +262,101 @@ def test_plan_sections_are_declared_once(be):
             if isinstance(n, ast.Assign) and getattr(n.targets[0], "id", None) == "lens"]
     assert len(lens) == 1 and lens[0].keys
     assert {k.value for k in lens[0].keys} <= set(be.PLAN_SECTIONS)
+
+
+def path_edges(graph):
+    """(N, ri, rj) of a named edge set of PATH_TABLE: ranks of the two-way edges."""
+    import torch
+    from mast3r_slam_amd import synthetic
+
+    kind, N = graph
+    if kind == "chain":  # consecutive keyframes only
+        ii, jj = list(range(N - 1)), list(range(1, N))
+    elif kind == "chain+loops":  # and a few loop closures
+        ii, jj = synthetic.make_edges(N, torch.Generator().manual_seed(N + 7), loop_frac=0.01)
+    elif kind == "complete":  # every pair (test_gn_over_capacity_plan_takes_dense_fallback)
+        ii, jj = [i for j in range(N) for i in range(j)], [j for j in range(N) for i in range(j)]
+    elif kind == "few-loops":  # a loop closure at every tenth keyframe
+        ii, jj = synthetic.make_edges(N, torch.Generator().manual_seed(N + 7), loop_frac=0.1)
+    else:  # "loops": make_graph's default edge set, seed = N
+        ii, jj = synthetic.make_edges(N, torch.Generator().manual_seed(N + 7))
+    return N, np.array(ii + jj, np.int32), np.array(jj + ii, np.int32)
+
+
+# (edge set, knobs, library, the solve path). The names are the parent
+# commit's: its two expressions (the scheduled / split choice of
+# build_plan_meta and the launch branches of gn_solve_impl) evaluated on these
+# rows gave profiles/solve_path/paths_parent.txt, which this table equals.
+# Rows with test-only knobs run on the test library. 63 keyframes is a size at
+# which the factor fits the LDS and the plan beside it does not ("lds").
+PATH_TABLE = [
+    (("chain", 6), {}, "product", "lds_plan"),
+    (("loops", 32), {}, "product", "lds_plan"),
+    (("loops", 63), {}, "product", "lds"),
+    (("loops", 140), {"dense_tail_min": 8}, "product", "chip"),
+    (("loops", 140), {"dense_tail_min": 0}, "product", "chip"),
+    (("loops", 140), {"dense_tail_min": 8}, "test", "chip"),
+    (("loops", 140), {"dense_tail_min": 8, "cols": 0}, "test", "global_split"),
+    (("loops", 140), {"dense_tail_min": 8, "cols": 0, "tail_mfma": 0}, "test", "global_split"),
+    (("loops", 140), {"dense_tail_min": 8, "cols": 0, "border_split": 0}, "test", "global"),
+    (("loops", 140), {"dense_tail_min": 0, "cols": 0}, "test", "global"),
+    (("loops", 140), {"dense_tail_min": 8, "dense": 1}, "test", "dense"),
+    (("loops", 63), {"cols": 0}, "test", "lds"),
+    (("complete", 201), {}, "product", "dense"),
+    (("chain+loops", 520), {}, "product", "global"),
+    (("few-loops", 520), {"dense_tail_min": 8}, "product", "global_split"),
+    (("loops", 520), {"dense_tail_min": 8}, "product", "dense"),  # its plan exceeds the workspace's capacity
+    (("chain", 1), {}, "product", "pending"),
+]
+
+
+def path_row_id(row):
+    (kind, N), knobs_, lib, _ = row
+    return "-".join([f"{kind}{N}", lib] + [f"{k}={v}" for k, v in knobs_.items()])
+
+
+def solve_path_rows():
+    """The row list M3S_SOLVE_PATHS of csrc/gn/plan.h, in order."""
+    import os
+    import re
+
+    path = os.path.join(os.path.dirname(__file__), "..", "mast3r-slam-ysh_amd", "csrc", "gn", "plan.h")
+    text = re.sub(r"/\*.*?\*/", "", open(path).read().replace("\\\n", " "))
+    (rows,) = re.findall(r"^#define M3S_SOLVE_PATHS\(X\)(.*)$", text, re.M)
+    assert re.sub(r"X\(\w+\)|\s", "", rows) == ""  # nothing but rows in the list
+    return re.findall(r"X\((\w+)\)", rows)
+
+
+@pytest.mark.parametrize("row", PATH_TABLE, ids=path_row_id)
+def test_plan_names_its_solve_path(be, row, knobs, request):
+    """The path build_plan_meta writes into the plan (m3s_gn_plan_path_debug;
+    host only) for each row of PATH_TABLE, on the library the row names."""
+    graph, knobs_, lib, want = row
+    if lib == "test":
+        request.getfixturevalue("test_lib")
+    for name, value in knobs_.items():
+        knobs(name, value)
+    N, ri, rj = path_edges(graph)
+    assert be.plan_path(N, 4, ri, rj) == want
+
+
+def test_solve_path_names_come_from_the_row_list(be, knobs, request):
+    """Every name the export gives over PATH_TABLE is a row of
+    M3S_SOLVE_PATHS, the table reaches every row, and bad arguments give no
+    name."""
+    rows = solve_path_rows()
+    assert len(set(rows)) == len(rows) == 7
+    seen = set()
+    for graph, knobs_, lib, _ in PATH_TABLE:
+        if lib == "test":
+            continue  # the product library's own names; test_plan_names_its_solve_path covers the rest
+        for name, value in knobs_.items():
+            knobs(name, value)
+        N, ri, rj = path_edges(graph)
+        seen.add(be.plan_path(N, 4, ri, rj))
+    assert seen <= set(rows)
+    assert {want for *_, want in PATH_TABLE} == set(rows)
+    with pytest.raises(RuntimeError):
+        be.plan_path(0, 4, [], [])
+    with pytest.raises(RuntimeError):
+        be.plan_path(6, 4, [0, 7], [1, 2])  # a rank outside [0, N)
